@@ -14,10 +14,14 @@ cannot gain there).  Per step one RCCL exchange: the ranks' system vectors + ene
 their newest-frame candidates, all-gathered in one group call; every rank sums the vectors in
 rank order and selects the threshold beside the solve.  --workload ba-kitti runs the same window at KITTI 1232x368 (C5's BA half).
 
-JSON line fields follow the driver contract; `roofline` is for the dominant kernel
-(hs_k_linearize, timed with HIP events on the context's own stream), `cpu_baseline` is
-the oracle's C++ restatement of the reference SSE/IndexThreadReduce path timed on
-this host (rank 0, N=1 only).
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+JSON line: `value`, `ms_per_step` and the workload's `config`.  `--dump-outputs DIR` also writes
+what the last timed step left for the caller as DIR/<name>.npy.  Everything else is measured only
+with `--full`, in runs of their own after the timed loop: `roofline` for the dominant kernel
+(hs_k_linearize, timed with HIP events on the context's own stream), the per-phase split, the
+whole-call times, the other scaling modes (N > 1), and `cpu_baseline`, the oracle's C++
+restatement of the reference SSE/IndexThreadReduce path timed on this host (rank 0, N=1 only).
+Without `--full` those fields are null.
 """
 from __future__ import annotations
 
@@ -38,6 +42,28 @@ BYTES_PER_PRES = 448      # algorithmic bytes per point-residu
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md)
 STRONG_LARGE_POINTS = 200000  # N > 1: the window whose strong scaling is reported beside the metric's own
 TRACK_BYTES_PER_POINT_PASS = 64  # CoarseTracker bytes per reference point per calcRes+GS pass
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: upper bound on what one run writes
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(directory, arrays: dict, rank: int = 0):
+    """--dump-outputs: `arrays` (name -> what the last timed step left for the caller) as DIR/<name>.npy, float32
+    or float64 (integer and flag arrays as float64 / float32 values), ranks above 0 as DIR/<name>_rank<r>.npy.  An
+    array above its share of DUMP_BUDGET_BYTES is cut to a fixed sample of its rows (indices drawn once from
+    DUMP_SAMPLE_SEED, ascending), the same rows in every run with the same arguments."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.atleast_1d(np.asarray(a))
+        if a.dtype != np.float32 and a.dtype != np.float64:
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        if a.nbytes > share:
+            row = max(1, a.nbytes // len(a))
+            keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(a), max(1, share // row), replace=False))
+            a = a[keep]
+        np.save(os.path.join(directory, name + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
 
 
 def pmc_traffic(points, kernel: str = "hs_k_lin"):
@@ -242,7 +268,10 @@ def bench_trace(args):
         kern += ms
         steps += st
     dt = time.perf_counter() - t0
-    counts = t.traceNewCoarse(s.KRKi, s.Kt, s.aff)  # one more (second-trace state) only for the tallies
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, t.points())
+    # --full: one more (second-trace state) only for the tallies
+    counts = t.traceNewCoarse(s.KRKi, s.Kt, s.aff) if args.full else None
     kern_ms = kern / args.steps
     algo_bytes = steps / args.steps * TRACE_BYTES_PER_STEP
     achieved = algo_bytes / (kern_ms * 1e-3) / 1e9
@@ -254,16 +283,22 @@ def bench_trace(args):
         "config": {"workload": "C5 (BASELINE.json configs[4]) traceOn part: ctor + first traceOn of 20k immature "
                                "points, 8 host KFs, 1232x368", "points": s.n_points, "hosts": s.n_hosts,
                    "search_steps_per_trace": steps // args.steps, "parallelism": "single GPU"},
-        "roofline": dict({"bound": "hbm", "kernel": "hs_k_trace_on", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_roof("trace", "hs_k_trace_on").get("hbm_bytes_per_launch", pmc_traffic("trace", "hs_k_trace_on")[0]),
-                     "bytes_per_unit": TRACE_BYTES_PER_STEP, "unit_of_bytes": "discrete-search step (GN taps excluded)",
-                     "avg_launch_ms": kern_ms, "counters": pmc_roof("trace", "hs_k_trace_on")},
-                     **roof_binding(pmc_roof("trace", "hs_k_trace_on"), achieved / HBM_PEAK_GBS)),
-        "second_trace_counts": dict(zip(("good", "oob", "outlier", "skipped", "badcondition", "uninitialized"),
-                                        map(int, counts))),
+        "roofline": None,
+        "second_trace_counts": None,
         "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full:
+        res["roofline"] = dict(
+            {"bound": "hbm", "kernel": "hs_k_trace_on", "achieved": achieved, "peak": HBM_PEAK_GBS,
+             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+             "traffic": pmc_roof("trace", "hs_k_trace_on").get("hbm_bytes_per_launch",
+                                                               pmc_traffic("trace", "hs_k_trace_on")[0]),
+             "bytes_per_unit": TRACE_BYTES_PER_STEP, "unit_of_bytes": "discrete-search step (GN taps excluded)",
+             "avg_launch_ms": kern_ms, "counters": pmc_roof("trace", "hs_k_trace_on")},
+            **roof_binding(pmc_roof("trace", "hs_k_trace_on"), achieved / HBM_PEAK_GBS))
+        res["second_trace_counts"] = dict(zip(("good", "oob", "outlier", "skipped", "badcondition", "uninitialized"),
+                                              map(int, counts)))
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle_ffi import OracleTracer  # test infrastructure: the CPU baseline leg only
         o = OracleTracer(s.width, s.height, fast=True)
@@ -303,18 +338,22 @@ def bench_track(args):
     for _ in range(args.steps):
         ok, T, a = ct.trackNewestCoarse(T0, [0.0, 0.0], s.n_levels - 1, minRes)
     dt = time.perf_counter() - t0
-    ct.set_event_timing(True)
-    dev = 0.0
-    for _ in range(args.steps):
-        ct.trackNewestCoarse(T0, [0.0, 0.0], s.n_levels - 1, minRes)
-        dev += ct.last_ms()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"ok": [ok], "pose": T, "aff": a})
     # roofline: 64 B of algorithmic traffic and ~230 FLOP per point-pass (reference point
     # x calcRes(+calcGSSSE) pass); the units come from the kernel's own pass counters
     _, passes, point_passes = ct.last_stats(0)
-    dev_ms = dev / args.steps
-    if dev_ms <= 0:  # no device timing (HS_TRK_NOEVT=1): the host clock per call
-        dev_ms = dt * 1e3 / args.steps
-    achieved = point_passes * TRACK_BYTES_PER_POINT_PASS / (dev_ms * 1e-3) / 1e9
+    dev_ms = achieved = None
+    if args.full:  # the device time per track: an untimed loop of its own with the event pair on
+        ct.set_event_timing(True)
+        dev = 0.0
+        for _ in range(args.steps):
+            ct.trackNewestCoarse(T0, [0.0, 0.0], s.n_levels - 1, minRes)
+            dev += ct.last_ms()
+        dev_ms = dev / args.steps
+        if dev_ms <= 0:  # no device timing (HS_TRK_NOEVT=1): the host clock per call
+            dev_ms = dt * 1e3 / args.steps
+        achieved = point_passes * TRACK_BYTES_PER_POINT_PASS / (dev_ms * 1e-3) / 1e9
     res = {
         "metric": "frames tracked/sec (CoarseTracker::trackNewestCoarse, C2 640x480, 5 levels)",
         "value": args.steps / dt, "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -326,7 +365,8 @@ def bench_track(args):
                    "timing": "value / ms_per_step: host clock over the timed loop in the library's default mode "
                              "(no per-call event pair, done-word results); device_ms_per_track: the event pair "
                              "(hs_tracker_set_event_timing), in an untimed loop after it"},
-        "roofline": {"bound": "hbm", "kernel": "hs_k_track", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "roofline": None if not args.full else {
+                     "bound": "hbm", "kernel": "hs_k_track", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
                      "traffic": pmc_roof("track", "hs_k_track").get("hbm_bytes_per_launch",
                                                                     pmc_traffic("track", "hs_k_track")[0]),
@@ -338,7 +378,7 @@ def bench_track(args):
                      "timing": "HIP events around the single hs_k_track launch of each trackNewestCoarse"},
         "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle_ffi import OracleTracker  # test infrastructure: the CPU baseline leg only
         o = OracleTracker(s.width, s.height, s.K4, s.n_levels, fast=True)
@@ -381,6 +421,8 @@ def bench_act(args):
     for _ in range(args.steps):
         r = g.activatePointsMT(*call)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r)
     n_opt = int((r["action"] == 2).sum() + 0)
     res = {
         "metric": "point activations/sec (System::activatePointsMT, KITTI 1232x368 window, 14k immature points)",
@@ -392,7 +434,7 @@ def bench_act(args):
                    "immature_points": len(s.imm_u)},
         "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from test_act import oracle_tracer  # test infrastructure: the CPU baseline leg only
         o = oracle_tracer(s)
@@ -430,6 +472,8 @@ def bench_refine(args):
         T, vid, good, it, sn = g.Refine(s.T_init)
         dt += time.perf_counter() - t0
         dev += g.last_ms()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pose": T, "videpth": vid, "good": good, "iterations": [it], "snapped": [sn]})
     passes = it + 1  # calcResAndGS evaluations per Refine
     res = {
         "metric": "refinements/sec (DirectRefinement::Refine, 640x480 pair, 2000 keypoints)",
@@ -442,7 +486,7 @@ def bench_refine(args):
                    "device_us_per_pass": dev / args.steps * 1e3 / passes},
         "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle_ffi import OracleRefiner  # test infrastructure: the CPU baseline leg only
         n, tt = 0, 0.0
@@ -480,6 +524,8 @@ def bench_select(args):
         dev += sel.last_stats()[0]
         fid += 1
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # the timed call asks for no map (want_map=False): the count and the potential it left
+        dump_outputs(args.dump_outputs, {"n_selected": [n_sel], "current_potential": [sel.currentPotential]})
     res = {
         "metric": "frames selected/sec (PixelSelector::makeMaps, 640x480, density 2000)",
         "value": args.steps / dt, "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -489,7 +535,7 @@ def bench_select(args):
                    "selected": n_sel, "device_ms_per_frame": dev / args.steps},
         "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from oracle_ffi import PixelSelector as OracleSelector, dir_pyramid  # the CPU baseline leg only
         pyrs = [dir_pyramid(f, 3) for f in frames]
@@ -531,6 +577,11 @@ def bench_keyframe(args):
     for k in range(7 + args.warmup, n_kf):
         rows.append(drv.add_keyframe(k))
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # the last keyframe's optimize energies, its tail's outputs, the window's frames after it
+        fr = drv.ba.frames()
+        dump_outputs(args.dump_outputs, {"energies": rows[-1]["energies"], "tail_HdiF": drv.last_tail["HdiF"],
+                                         "tail_drop": drv.last_tail["drop"], "frame_state": fr["state"],
+                                         "frame_pose": fr["pose"], "calib": fr["calib"]})
     lib = np.array([r["lib_s"] for r in rows]) * 1e3
     ph = {p: np.array([r["phase_s"].get(p, 0.0) for r in rows]) * 1e3
           for p in ("setup", "optimize", "tail", "post", "track_frame")}
@@ -560,7 +611,7 @@ def bench_keyframe(args):
         "roofline": None,
         "cpu_baseline": None,
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         cb = cpu_baseline(args.points, args.cpu_seconds)
         # a keyframe's BA on the CPU path: optimize(6) = the GN iterations run (the same break test) after the initial
         # linearization, plus the tail's linearizeAll(true): (iterations + 1) GN-iteration equivalents of the same
@@ -690,7 +741,7 @@ def run_window(args, n_window, kitti, world, rank, local, dist):
 
     barrier()
     t0 = time.perf_counter()
-    ba.iterate(args.warmup, args.steps)  # K device-resident GN iterations, one host sync at the end
+    energies = ba.iterate(args.warmup, args.steps)  # K device-resident GN iterations, one host sync at the end
     t1 = time.perf_counter()
     barrier()
     dt = t1 - t0
@@ -703,7 +754,7 @@ def run_window(args, n_window, kitti, world, rank, local, dist):
         nr = torch.tensor([shard.n_res], dtype=torch.int64, device="cuda")
         dist.all_reduce(nr)
         n_res_total = int(nr.item())
-    return dict(ba=ba, shard=shard, dt=dt, n_res_total=n_res_total, n_window=n_window, ranks=ranks,
+    return dict(ba=ba, shard=shard, dt=dt, n_res_total=n_res_total, n_window=n_window, ranks=ranks, energies=energies,
                 value=n_res_total * args.steps / dt, ms_per_step=dt * 1e3 / args.steps)
 
 
@@ -720,6 +771,50 @@ def phase_split(ba, first, steps):
     return {"solve_step_kernel": t["solve_ms"] / n, "linearize_kernel": t["linearize_ms"] / n,
             "accumulate_stitch": t["acc_stitch_ms"] / n, "event_timed_steps": t["timed_iters"],
             "timing": "HIP event pairs per launch group in an untimed loop after the timed one"}
+
+
+def linearize_roofline(args, ba, shard, kitti, world, split, lin_loop_ms):
+    """--full: the `roofline` entry of the BA workloads, for the linearize kernel of the live window `ba`: its launch
+    duration from back-to-back launches of its own after the timed loop, the committed counters beside it."""
+    # the same kernel, same inputs, launched back to back between one event pair: the launch duration
+    # rocprofv3 reports (the in-loop pairs add the event-record overhead to a ~9 us kernel)
+    lin_ms = ba.time_linearize(max(64, args.steps))
+    achieved = BYTES_PER_PRES * shard.n_res / (lin_ms * 1e-3) / 1e9
+    lin_kernel = ba.partition()["kernel"]  # hs_k_lin (one point per wave) or hs_k_lin8 (8 points per wave)
+    roof_ctr = pmc_roof(f"kitti{args.points}" if kitti else args.points, lin_kernel) if world == 1 else {}
+    traffic, traffic_src = ((roof_ctr["hbm_bytes_per_launch"], roof_ctr["source"]) if "hbm_bytes_per_launch" in roof_ctr
+                            else pmc_traffic(f"kitti{args.points}" if kitti else args.points, lin_kernel) if world == 1
+                            else (None, None))
+    roofline = {
+        "bound": "hbm",
+        "kernel": lin_kernel,
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "traffic": traffic,
+        "traffic_source": traffic_src,
+        "bytes_per_unit": BYTES_PER_PRES,
+        "units_per_launch": shard.n_res,
+        "avg_launch_ms": lin_ms,
+        "avg_launch_ms_in_loop_events": lin_loop_ms,
+        "timing": f"HIP events on the context stream around back-to-back {lin_kernel} launches (fused "
+                  "linearize + applyRes + top / Schur accumulation into block partials)",
+        # the GN loop's launch also applies the previous solve's point step (resubstituteFPt, fused): it reads the
+        # last linearization's JpJdF (32 B per residual) and the step's chain heads every point group
+        "avg_launch_ms_gn_loop": (split or {}).get("linearize_kernel"),
+        "frac_gn_loop": (BYTES_PER_PRES * shard.n_res / ((split or {})["linearize_kernel"] * 1e-3) / 1e9
+                         / HBM_PEAK_GBS) if (split or {}).get("linearize_kernel") else None,
+        "gn_loop_timing": "the same kernel inside the fused GN loop (with the point step of the previous solve), "
+                          "HIP event pairs per launch in an untimed loop after the timed one (+~3 us event "
+                          "overhead per launch)",
+        "counters": roof_ctr,
+        "limiter_note": "one point per wave at 2k: dependent memory round trips (the step is a chain of 4 "
+                        "dependent launches, the single-workgroup fp64 solve the longest)" if shard.n_points < 60000
+                        else "VALU issue + gather latency at occupancy 2 (DESIGN.md §9)",
+    }
+    roofline.update(roof_binding(roof_ctr, achieved / HBM_PEAK_GBS))
+    return roofline
 
 
 def optimize_calls(scene, reps=15):
@@ -773,14 +868,22 @@ def main():
                     help="strong (default): `value` is the metric's own 8 KF x --points window sharded over the N "
                          "GPUs; weak: --points per GPU (a window of --points x N).  The other one is measured too "
                          "(N > 1) and reported beside it")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need, in runs of "
+                         "their own: roofline of the dominant kernel, per-phase split, whole-call times, the other "
+                         "scaling modes (N > 1), the CPU baseline.  Without it those fields of the JSON line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left for the caller as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: larger arrays as a fixed seeded sample of their rows)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: time budget of the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--phase-events", type=int, default=None, choices=(0, 1, 2),
                     help="HIP event pairs inside the timed GN loop (sets HS_EVENT_TIMING; default: the environment's "
                          "value, else 0 = none; each pair adds ~2 us per step), 1 linearize only, 2 every phase")
-    ap.add_argument("--no-phase-split", action="store_true", help="skip the untimed event-timed phase-split loop")
+    ap.add_argument("--no-phase-split", action="store_true",
+                    help="--full without the untimed event-timed phase-split loop and the whole-call times")
     ap.add_argument("--no-large-strong", action="store_true",
-                    help="N > 1: skip the strong-scaling run of the 200k-point window reported beside `value`")
+                    help="--full, N > 1: skip the strong-scaling run of the 200k-point window reported beside `value`")
     ap.add_argument("--plumbing-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:
@@ -821,24 +924,26 @@ def main():
     n_window = args.points * world if args.scaling == "weak" else args.points
     run = run_window(args, n_window, kitti, world, rank, local, dist)
     ba, shard = run["ba"], run["shard"]
-    tim = ba.timings()
-    nt = max(1, tim["timed_iters"])
-    # per-launch event pairs inside the GN loop (+~3 us event overhead); None without --phase-events
-    lin_loop_ms = tim["linearize_ms"] / nt if tim["timed_iters"] > 0 else None
-    # continues the timed loop's GN iterations (collective on N > 1: every rank runs it)
-    split = None if args.no_phase_split else phase_split(ba, args.warmup + args.steps, min(max(args.steps, 20), 100))
-    # the same kernel, same inputs, launched back to back between one event pair: the launch duration
-    # rocprofv3 reports (the in-loop pairs add the event-record overhead to a ~9 us kernel)
-    lin_ms = ba.time_linearize(max(64, args.steps))
-    achieved = BYTES_PER_PRES * shard.n_res / (lin_ms * 1e-3) / 1e9
-    lin_kernel = ba.partition()["kernel"]  # hs_k_lin (one point per wave) or hs_k_lin8 (8 points per wave)
-    roof_ctr = pmc_roof(f"kitti{args.points}" if kitti else args.points, lin_kernel) if world == 1 else {}
-    traffic, traffic_src = ((roof_ctr["hbm_bytes_per_launch"], roof_ctr["source"]) if "hbm_bytes_per_launch" in roof_ctr
-                            else pmc_traffic(f"kitti{args.points}" if kitti else args.points, lin_kernel) if world == 1
-                            else (None, None))
+    if args.dump_outputs:
+        # what the timed loop's caller holds after its last step: the steps' energies (hs_ba_iterate's output), and
+        # the window the last step left, through the read-back calls (frames, points, residuals of this rank's shard)
+        out = {"energies": run["energies"]}
+        for group, arrs in (("frames", ba.frames()), ("points", ba.points()), ("residuals", ba.residuals())):
+            out.update({f"{group}_{k}": v for k, v in arrs.items()})
+        dump_outputs(args.dump_outputs, out, rank)
+    split = roofline = None
+    if args.full:
+        tim = ba.timings()
+        nt = max(1, tim["timed_iters"])
+        # per-launch event pairs inside the GN loop (+~3 us event overhead); None without --phase-events
+        lin_loop_ms = tim["linearize_ms"] / nt if tim["timed_iters"] > 0 else None
+        # continues the timed loop's GN iterations (collective on N > 1: every rank runs it)
+        if not args.no_phase_split:
+            split = phase_split(ba, args.warmup + args.steps, min(max(args.steps, 20), 100))
+        roofline = linearize_roofline(args, ba, shard, kitti, world, split, lin_loop_ms)
     ba.close()
     other = large = None
-    if world > 1:  # the other scaling mode, same ranks and communicator set-up, reported beside `value`
+    if world > 1 and args.full:  # the other scaling mode, same ranks and communicator set-up, reported beside `value`
         mode = "weak" if args.scaling == "strong" else "strong"
         o = run_window(args, args.points * world if mode == "weak" else args.points, kitti, world, rank, local, dist)
         other = {"scaling": mode, "value": o["value"], "ms_per_step": o["ms_per_step"], "points": o["n_window"],
@@ -888,47 +993,19 @@ def main():
             "launcher": "bench.py child ranks" if env_world is None and world > 1 else (
                 "torch.distributed.run" if world > 1 else "single process"),
         },
-        "roofline": {
-            "bound": "hbm",
-            "kernel": lin_kernel,
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "bytes_per_unit": BYTES_PER_PRES,
-            "units_per_launch": shard.n_res,
-            "avg_launch_ms": lin_ms,
-            "avg_launch_ms_in_loop_events": lin_loop_ms,
-            "timing": f"HIP events on the context stream around back-to-back {lin_kernel} launches (fused "
-                      "linearize + applyRes + top / Schur accumulation into block partials)",
-            # the GN loop's launch also applies the previous solve's point step (resubstituteFPt, fused): it reads the
-            # last linearization's JpJdF (32 B per residual) and the step's chain heads every point group
-            "avg_launch_ms_gn_loop": (split or {}).get("linearize_kernel"),
-            "frac_gn_loop": (BYTES_PER_PRES * shard.n_res / ((split or {})["linearize_kernel"] * 1e-3) / 1e9
-                             / HBM_PEAK_GBS) if (split or {}).get("linearize_kernel") else None,
-            "gn_loop_timing": "the same kernel inside the fused GN loop (with the point step of the previous solve), "
-                              "HIP event pairs per launch in an untimed loop after the timed one (+~3 us event "
-                              "overhead per launch)",
-            "counters": roof_ctr,
-            "limiter_note": "one point per wave at 2k: dependent memory round trips (the step is a chain of 4 "
-                            "dependent launches, the single-workgroup fp64 solve the longest)" if shard.n_points < 60000
-                            else "VALU issue + gather latency at occupancy 2 (DESIGN.md §9)",
-        },
+        "roofline": roofline,
         "phase_ms_per_step": split,
         "cpu_baseline": None,
     }
-    result["roofline"].update(roof_binding(roof_ctr, achieved / HBM_PEAK_GBS))
     if other is not None:
         result[f"{other['scaling']}_scaling"] = other
     if large is not None:
         result["strong_scaling_200k"] = large
-    if world == 1 and not args.no_phase_split:
+    if args.full and world == 1 and not args.no_phase_split:
         calls = optimize_calls(shard)
         calls["six_steps_ms"] = 6 * run["ms_per_step"]
         result["calls_ms"] = calls
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(n_window, args.cpu_seconds, kitti)
         speedup(result)
     if rank == 0:

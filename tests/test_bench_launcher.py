@@ -55,6 +55,32 @@ def test_single_gpu_workloads_reject_gpus():
     assert r.returncode != 0 and "single-GPU" in (r.stderr + r.stdout)
 
 
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array lands as <name>.npy in float32 / float64 with its values kept, an array above its
+    share of the budget as the same ascending sample of its rows in every run, other ranks under their own names."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)  # 4 arrays: 1000 B each
+    big = np.arange(3000, dtype=np.float32).reshape(1000, 3)
+    arrays = {"state": np.array([0, 1, 2, 255], np.uint8), "count": [7], "energy": np.array([1.5, 2.5]), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["big.npy", "count.npy", "energy.npy", "state.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["state.npy"].tolist() == [0, 1, 2, 255] and got["count.npy"].tolist() == [7]
+    assert got["energy.npy"].dtype == np.float64 and got["energy.npy"].tolist() == [1.5, 2.5]
+    s = got["big.npy"]
+    assert s.shape == (1000 // 12, 3) and sum(a.nbytes for a in got.values()) <= 4000
+    rows = (s[:, 0] / 3).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s, big[rows])  # whole rows of the array, in its order
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    bench.dump_outputs(str(tmp_path / "a"), {"energy": [3.0]}, rank=2)
+    assert np.load(tmp_path / "a" / "energy_rank2.npy").tolist() == [3.0]
+    assert np.load(tmp_path / "a" / "energy.npy").tolist() == [1.5, 2.5]
+
+
 def test_count_gpus_reads_the_kfd_topology(tmp_path, monkeypatch):
     """The launcher counts GPUs from the KFD topology (nodes with SIMDs), narrowed by the visibility variables,
     without loading a HIP library."""

@@ -11,10 +11,10 @@ timeout -k 10 600 python -u -m pytest $TESTS -m gpu -x -v --timeout 120 --timeou
 rc=$?
 echo "pytest rc=$rc"; grep -E "FAIL|ERROR|Error|assert|passed|failed" $OUT/pytest.txt | head -20
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 200 python bench.py --steps 100 --warmup 5 --no-cpu > $OUT/b2k.json 2> $OUT/b2k.err || { echo "bench failed"; tail -20 $OUT/b2k.err; exit 1; }
-timeout -k 10 200 python bench.py --workload track --steps 20 --warmup 3 --no-cpu > $OUT/track.json 2> $OUT/track.err || { echo "bench track failed"; tail -20 $OUT/track.err; exit 1; }
+timeout -k 10 200 python bench.py --full --steps 100 --warmup 5 --no-cpu > $OUT/b2k.json 2> $OUT/b2k.err || { echo "bench failed"; tail -20 $OUT/b2k.err; exit 1; }
+timeout -k 10 200 python bench.py --full --workload track --steps 20 --warmup 3 --no-cpu > $OUT/track.json 2> $OUT/track.err || { echo "bench track failed"; tail -20 $OUT/track.err; exit 1; }
 for P in 20000 200000; do
-  timeout -k 10 200 python bench.py --steps 30 --warmup 3 --no-cpu --points $P > $OUT/p$P.json 2> $OUT/p$P.err || { echo "bench $P failed"; tail -20 $OUT/p$P.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --steps 30 --warmup 3 --no-cpu --points $P > $OUT/p$P.json 2> $OUT/p$P.err || { echo "bench $P failed"; tail -20 $OUT/p$P.err; exit 1; }
 done
 python3 - <<PY
 import json

@@ -11,7 +11,7 @@ echo "pytest rc=$rc"; grep -E "PASS|FAIL|ERROR|Error|assert" $OUT/pytest_lin8.tx
 if [ $rc -gt 1 ]; then exit $rc; fi
 for P in 2000 20000 200000; do
   for M in 0 1; do
-    HS_LIN8=$M timeout -k 10 200 python bench.py --steps 30 --warmup 3 --no-cpu --points $P > $OUT/p${P}_l$M.json 2> $OUT/p${P}_l$M.err || { echo "bench $P $M failed"; tail -20 $OUT/p${P}_l$M.err; exit 1; }
+    HS_LIN8=$M timeout -k 10 200 python bench.py --full --steps 30 --warmup 3 --no-cpu --points $P > $OUT/p${P}_l$M.json 2> $OUT/p${P}_l$M.err || { echo "bench $P $M failed"; tail -20 $OUT/p${P}_l$M.err; exit 1; }
     python3 -c "
 import json,sys
 d=json.loads(open('$OUT/p${P}_l$M.json').read().strip().splitlines()[-1])

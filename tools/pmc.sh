@@ -3,7 +3,7 @@
 # WRITE_SIZE in SEPARATE --pmc passes (FETCH_SIZE uses 3 TCC counters, WRITE_SIZE 2), kernel trace
 # only, no sys/runtime trace.  usage: tools/pmc.sh TAG [bench args...]
 TAG=${1:-pmc}; shift
-ARGS=${@:---steps 20 --warmup 2 --no-cpu}
+ARGS=${@:---full --steps 20 --warmup 2 --no-cpu}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -13,9 +13,9 @@ timeout -s KILL 60 rocprofv3 -L > $OUT/counters.txt 2>&1 || echo "counter list r
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
 for K in $KEYS; do
   case $K in
-    kitti*) ARGS="--workload ba-kitti --points ${K#kitti} --steps 10 --warmup 2 --no-cpu --no-phase-split" ;;
-    trace|track) ARGS="--workload $K --steps 5 --warmup 1 --no-cpu" ;;
-    *) ARGS="--points $K --steps 10 --warmup 2 --no-cpu --no-phase-split" ;;
+    kitti*) ARGS="--full --workload ba-kitti --points ${K#kitti} --steps 10 --warmup 2 --no-cpu --no-phase-split" ;;
+    trace|track) ARGS="--full --workload $K --steps 5 --warmup 1 --no-cpu" ;;
+    *) ARGS="--full --points $K --steps 10 --warmup 2 --no-cpu --no-phase-split" ;;
   esac
   mkdir -p $OUT/p$K
   for P in FETCH_SIZE WRITE_SIZE SQ; do

@@ -80,7 +80,7 @@ def summarise(d):
 def main():
     d, keys = sys.argv[1], sys.argv[2:]
     print(json.dumps({"source": "tools/archive/r04_pmc.sh: rocprofv3 --kernel-trace --stats --pmc, separate FETCH_SIZE / "
-                                "WRITE_SIZE / SQ+GRBM passes over `python3 bench.py --no-cpu` (see pmc_roof.py)",
+                                "WRITE_SIZE / SQ+GRBM passes over `python3 bench.py --full --no-cpu` (see pmc_roof.py)",
                       "keys": {k: summarise(os.path.join(d, "p" + k)) for k in keys}}, indent=1))
 
 

@@ -47,7 +47,7 @@ def main():
     if sys.argv[1] == "--sizes":  # DIR/p<N>/{FETCH_SIZE,WRITE_SIZE} for each size N -> bench.py's committed format
         d, sizes = sys.argv[2], sys.argv[3:]
         print(json.dumps({
-            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes over `python3 bench.py --no-cpu "
+            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes over `python3 bench.py --full --no-cpu "
                       "--points N` (tools/archive/r03_pmc.sh; keys: C4 point counts, kitti<N>, trace, track); hbm_bytes_per_launch = 2*FETCH_SIZE + WRITE_SIZE (gfx950 "
                       "FETCH_SIZE half-count correction, MI355X_MICROARCH.md); FETCH_SIZE counts memory-side requests "
                       "incl. Infinity-Cache hits",
