@@ -14,6 +14,8 @@
 #include "../../include/hs_trace.h"
 #include "hs_trace_kernels.h"
 #include "hs_pyr_kernels.h"
+#include "../../include/hs_undist.h"
+#include "hs_undist_kernels.h"
 
 #define HS_MAXF_ACT 8                        // activation window (nF <= 8 keyframes)
 #define HS_ACT_LDS_MAP_MAX (156 * 1024)     // level-1 distance map in LDS up to this size
@@ -269,6 +271,19 @@ int hs_tracer_set_frame_raw(hs_tracer* t, const float* img) {
   TR_HIP(hipSetDevice(t->device));
   if (!t->d_raw) TR_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
   TR_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
+  float4* lv[1] = {t->d_new};
+  TR_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
+  TR_HIP(hipStreamSynchronize(t->stream));
+  t->have_frame = true;
+  return HS_OK;
+}
+
+int hs_tracer_set_frame_u8(hs_tracer* t, hs_undistorter* u, const uint8_t* raw) {
+  if (!t || !u || !raw) return cfail(HS_ERR_INVALID, "null argument");
+  TR_TRY(hs_undist_match(u, t->device, t->W, t->H));
+  TR_HIP(hipSetDevice(t->device));
+  if (!t->d_raw) TR_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
+  TR_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
   float4* lv[1] = {t->d_new};
   TR_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
   TR_HIP(hipStreamSynchronize(t->stream));

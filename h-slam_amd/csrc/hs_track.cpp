@@ -15,6 +15,8 @@
 #include "hs_ba_ctx.h"
 #include "hs_track_kernels.h"
 #include "hs_pyr_kernels.h"
+#include "../../include/hs_undist.h"
+#include "hs_undist_kernels.h"
 
 namespace {
 int tfail(int code, const std::string& msg) {
@@ -630,6 +632,19 @@ int hs_tracker_set_frame_raw(hs_tracker* t, const float* img, float ab_exposure)
   TS_HIP(hipSetDevice(t->device));
   if (!t->d_raw) TS_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
   TS_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
+  TS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
+  TS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
+  t->newExposure = ab_exposure;
+  t->haveFrame = true;
+  return HS_OK;
+}
+
+int hs_tracker_set_frame_u8(hs_tracker* t, hs_undistorter* u, const uint8_t* raw, float ab_exposure) {
+  if (!t || !u || !raw) return tfail(HS_ERR_INVALID, "null argument");
+  TS_TRY(hs_undist_match(u, t->device, t->W, t->H));
+  TS_HIP(hipSetDevice(t->device));
+  if (!t->d_raw) TS_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
+  TS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
   TS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
   TS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
   t->newExposure = ab_exposure;

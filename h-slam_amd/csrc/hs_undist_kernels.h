@@ -1,0 +1,30 @@
+// hs_undist_kernels.h — the fused photometric + geometric undistortion kernel (include/hs_undist.h) and the
+// launcher the contexts chain in front of hs_build_dir_pyramid.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+struct hs_undistorter;
+
+struct HsUndistArgs {
+  int w_in, h_in, n_out;
+  int passthrough;      // n_out == w_in * h_in, output pixel i = S(raw[i])
+  const uint8_t* raw;   // w_in * h_in
+  const int2* map;      // n_out: (cvRound(remap_x * 32), cvRound(remap_y * 32)), fixed at table upload
+  const float* Binv;    // 256, null = no gamma
+  const float* B;       // 256, null = no photometric tables (img8 = sat8(fImg))
+  const float* vinv;    // w_in * h_in, null = no vignette
+  float* fimg;          // n_out, nullable
+  uint8_t* img8;        // n_out, nullable
+};
+
+__global__ void hs_k_undistort(HsUndistArgs a);
+
+// Checks that u is on `device` with a w x h output; HS_ERR_INVALID with hs_last_error set otherwise.
+int hs_undist_match(const hs_undistorter* u, int device, int w, int h);
+// Enqueues on `stream`: upload of the raw u8 frame (null: keep the staged one) into u's input staging, then the kernel into d_fimg
+// (w_out*h_out floats, device) and d_img8 (nullable).  The caller synchronises `stream` before it returns to its
+// own caller (raw is the user's buffer, and the staging is reused by the next call).
+hipError_t hs_undist_enqueue(hs_undistorter* u, hipStream_t stream, const uint8_t* raw, float* d_fimg,
+                             uint8_t* d_img8);

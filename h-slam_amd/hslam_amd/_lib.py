@@ -56,6 +56,12 @@ class hs_params(C.Structure):
         ("gradDownweightPerLevel", C.c_float), ("selectDirectionDistribution", C.c_int)]
 
 
+class hs_undist_calib(C.Structure):  # include/hs_undist.h
+    _fields_ = [("model", C.c_int), ("w_in", C.c_int), ("h_in", C.c_int), ("w_out", C.c_int), ("h_out", C.c_int),
+                ("process", C.c_int), ("K_in", C.c_double * 4), ("dist", C.c_double * 4),
+                ("desired_K", C.c_double * 4)]
+
+
 # exported symbols of include/hs_ba.h (argument types)
 VP, I, D = C.c_void_p, C.c_int, C.c_double
 SIGNATURES = {
@@ -171,6 +177,19 @@ SIGNATURES = {
     "hs_refiner_get_points": ([VP, VP, VP, VP], I),
     "hs_refiner_get_log": ([VP, I, VP], I),
     "hs_refiner_last_ms": ([VP, VP], I),
+    # include/hs_undist.h
+    "hs_undist_make_remap": ([VP, VP, VP, VP], I),
+    "hs_undist_make_photometric": ([VP, VP, I, VP, VP, VP], I),
+    "hs_undistorter_create": ([VP, I, VP], I),
+    "hs_undistorter_destroy": ([VP], None),
+    "hs_undistorter_set_photometric": ([VP, VP, VP], I),
+    "hs_undistorter_set_remap": ([VP, VP, VP], I),
+    "hs_undistorter_get_K": ([VP, VP], I),
+    "hs_undistorter_get_remap": ([VP, VP, VP], I),
+    "hs_undistorter_apply": ([VP, VP, VP, VP], I),
+    "hs_undistorter_time_kernel": ([VP, VP, I, I, VP], I),
+    "hs_tracker_set_frame_u8": ([VP, VP, VP, C.c_float], I),
+    "hs_tracer_set_frame_u8": ([VP, VP, VP], I),
 }
 
 _lib = None

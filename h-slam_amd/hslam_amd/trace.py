@@ -101,6 +101,12 @@ class ImmatureTracer:
         assert a.shape == (self.H, self.W)
         check(self.lib.hs_tracer_set_frame_raw(self.h, ptr(a)))
 
+    def set_frame_u8(self, undistorter, raw):
+        """The frame to trace on as the camera's raw u8 frame, undistorted on the device (hs_tracer_set_frame_u8)."""
+        a = np.ascontiguousarray(raw, np.uint8)
+        assert a.shape == (undistorter.h_in, undistorter.w_in)
+        check(self.lib.hs_tracer_set_frame_u8(self.h, undistorter.h, ptr(a)))
+
     def traceNewCoarse(self, KRKi, Kt, aff, counts=True):
         hosts = hosts_array(KRKi, Kt, aff)
         c = np.zeros(6, np.int32)

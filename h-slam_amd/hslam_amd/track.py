@@ -66,6 +66,13 @@ class CoarseTracker:
         assert a.shape == (self.height, self.width)
         check(self.lib.hs_tracker_set_frame_raw(self.h, ptr(a), float(ab_exposure)))
 
+    def setNewFrameU8(self, undistorter, raw, ab_exposure):
+        """The frame to track as the camera's raw u8 frame: hslam_amd.undistort.Undistorter's kernel, then
+        Frame::CreateDirPyrs, both on the tracker's stream (hs_tracker_set_frame_u8)."""
+        a = np.ascontiguousarray(raw, dtype=np.uint8)
+        assert a.shape == (undistorter.h_in, undistorter.w_in)
+        check(self.lib.hs_tracker_set_frame_u8(self.h, undistorter.h, ptr(a), float(ab_exposure)))
+
     def setCoarseTrackingRefBA(self, ba, promote: bool, ab_exposure=1.0, aff_g2l=(0.0, 0.0)):
         """setCoarseTrackingRef from a BA context (hslam_amd.ba.BAWindow) on the device: the points with an IN
         residual into its newest frame, no host round trip.  promote: the frame last set here becomes the reference
