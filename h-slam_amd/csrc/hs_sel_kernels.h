@@ -56,3 +56,10 @@ __global__ void hs_k_sel_pick(HsSelArgs a);
 __global__ void hs_k_sel_subcount(HsSelSubArgs a);
 __global__ void hs_k_sel_subscan(HsSelSubArgs a);
 __global__ void hs_k_sel_subapply(HsSelSubArgs a);
+
+struct hs_selector;
+// The selection map of the selector's last make_maps where it lies on the device (W*H floats), and the event on the
+// selector's stream after which it is complete: a consumer's stream waits on it before it reads.  HS_ERR_INVALID
+// when the selector is not on `device` with a w x h image, HS_ERR_STATE before any make_maps.  The map is
+// overwritten by the next make_maps: the consumer has finished reading by then (single caller).
+int hs_select_device_map(hs_selector* s, int device, int w, int h, const float** d_map, hipEvent_t* ready);

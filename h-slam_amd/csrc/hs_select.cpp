@@ -63,6 +63,7 @@ struct hs_selector {
   int* d_tiles = nullptr;
   float last_ms = 0;
   int last_passes = 0;
+  bool have_map = false;  // d_map holds a finished make_maps (hs_select_device_map)
 };
 
 static int n4(int n, int pot) { return (n + 4 * pot - 1) / (4 * pot); }
@@ -277,6 +278,7 @@ int finish(hs_selector* s, float* map_out, int* n_selected, int n) {
     SL_HIP(hipMemcpyAsync(map_out, s->d_map, (size_t)s->W * s->H * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   SL_HIP(hipStreamSynchronize(s->stream));
   SL_HIP(hipEventElapsedTime(&s->last_ms, s->e0, s->e1));
+  s->have_map = true;
   if (n_selected) *n_selected = n;
   return HS_OK;
 }
@@ -299,6 +301,7 @@ extern "C" int hs_selector_make_maps(hs_selector* s, int frame_id, const float* 
   SL_HIP(hipMemcpyAsync(s->d_g[2], absg2, n2 * sizeof(float), hipMemcpyHostToDevice, s->stream));
   SL_HIP(hipEventRecord(s->e0, s->stream));
   s->last_passes = 0;
+  s->have_map = false;
   int n = 0;
   SL_TRY(make_maps(s, s->d_dI, 3, frame_id, density, recursions_left, th_factor, &n));
   return finish(s, map_out, n_selected, n);
@@ -314,10 +317,21 @@ extern "C" int hs_selector_make_maps_raw(hs_selector* s, int frame_id, const flo
   SL_HIP(hipEventRecord(s->e0, s->stream));
   SL_HIP(hs_build_dir_pyramid(s->stream, s->d_raw, s->W, s->H, 3, s->d_lvl, s->d_g));
   s->last_passes = 0;
+  s->have_map = false;
   int n = 0;
   SL_TRY(make_maps(s, reinterpret_cast<const float*>(s->d_lvl[0]), 4, frame_id, density, recursions_left, th_factor,
                    &n));
   return finish(s, map_out, n_selected, n);
+}
+
+int hs_select_device_map(hs_selector* s, int device, int w, int h, const float** d_map, hipEvent_t* ready) {
+  if (!s) return sfail(HS_ERR_INVALID, "null selector");
+  if (s->device != device) return sfail(HS_ERR_INVALID, "selector and consumer are on different devices");
+  if (s->W != w || s->H != h) return sfail(HS_ERR_INVALID, "selector size differs from the consumer's");
+  if (!s->have_map) return sfail(HS_ERR_STATE, "the selector has made no map (hs_selector_make_maps)");
+  *d_map = s->d_map;
+  *ready = s->e1;
+  return HS_OK;
 }
 
 extern "C" int hs_selector_get_potential(hs_selector* s, int* potential) {

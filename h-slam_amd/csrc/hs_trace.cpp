@@ -16,6 +16,8 @@
 #include "hs_pyr_kernels.h"
 #include "../../include/hs_undist.h"
 #include "hs_undist_kernels.h"
+#include "../../include/hs_extract.h"
+#include "hs_extract_kernels.h"
 
 #define HS_MAXF_ACT 8                        // activation window (nF <= 8 keyframes)
 #define HS_ACT_LDS_MAP_MAX (156 * 1024)     // level-1 distance map in LDS up to this size
@@ -236,6 +238,34 @@ int hs_tracer_add_points(hs_tracer* t, int n, const int* host, const float* u, c
   for (int i = 0; i < n; i++) t->max_host = std::max(t->max_host, host[i]);
   TR_TRY(launch_ctor(t, f, n));
   TR_HIP(hipStreamSynchronize(t->stream));  // host arrays may go away after return
+  t->n += n;
+  return HS_OK;
+}
+
+int hs_tracer_add_keys(hs_tracer* t, hs_extractor* e, int slot, int* n_added) {
+  if (!t || !e) return cfail(HS_ERR_INVALID, "null argument");
+  if (slot < 0 || slot >= HS_TRC_MAXHOST || !t->d_host_img[slot])
+    return cfail(HS_ERR_INVALID, "keys on a host slot without an image");
+  int dev = 0, w = 0, h = 0, n = 0;
+  const float *d_x = nullptr, *d_y = nullptr;
+  hipEvent_t ready = nullptr;
+  hs_extract_keys(e, &dev, &w, &h, &n, &d_x, &d_y, &ready);
+  if (dev != t->device) return cfail(HS_ERR_INVALID, "extractor and tracer are on different devices");
+  if (w != t->W || h != t->H) return cfail(HS_ERR_INVALID, "extractor size differs from the tracer's");
+  if (t->n + n > t->cap) return cfail(HS_ERR_INVALID, "point capacity exceeded");
+  if (n_added) *n_added = n;
+  if (n == 0) return HS_OK;
+  TR_HIP(hipSetDevice(t->device));
+  const int f = t->n;
+  // keys lie >= 19 px from every edge (include/hs_extract.h): add_points' border rule holds by construction
+  TR_HIP(hipStreamWaitEvent(t->stream, ready, 0));
+  TR_HIP(hipMemcpyAsync(t->d_u + f, d_x, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
+  TR_HIP(hipMemcpyAsync(t->d_v + f, d_y, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
+  TR_HIP(hs_extract_keys_consumed(e, t->stream));
+  TR_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_host + f), slot, n, t->stream));
+  TR_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_type + f), 0x3f800000, n, t->stream));  // my_type 1.f
+  t->max_host = std::max(t->max_host, slot);
+  TR_TRY(launch_ctor(t, f, n));
   t->n += n;
   return HS_OK;
 }

@@ -190,6 +190,15 @@ SIGNATURES = {
     "hs_undistorter_time_kernel": ([VP, VP, I, I, VP], I),
     "hs_tracker_set_frame_u8": ([VP, VP, VP, C.c_float], I),
     "hs_tracer_set_frame_u8": ([VP, VP, VP], I),
+    # include/hs_extract.h
+    "hs_extractor_create": ([VP, I, I, I, I, VP], I),
+    "hs_extractor_destroy": ([VP], None),
+    "hs_extractor_extract": ([VP, VP, VP, VP], I),
+    "hs_extractor_extract_selected": ([VP, VP, VP, VP], I),
+    "hs_extractor_extract_u8": ([VP, VP, VP, VP, VP], I),
+    "hs_extractor_get": ([VP] * 6, I),
+    "hs_extractor_last_stats": ([VP, VP], I),
+    "hs_tracer_add_keys": ([VP, VP, I, VP], I),
 }
 
 _lib = None

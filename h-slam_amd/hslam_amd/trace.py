@@ -84,6 +84,14 @@ class ImmatureTracer:
         check(self.lib.hs_tracer_add_points(self.h, len(h), ptr(h), ptr(uu), ptr(vv)))
         self.n += len(h)
 
+    def add_keys(self, extractor, slot: int) -> int:
+        """makeNewTraces' loop: new ImmaturePoint for every key of ``extractor``'s (FeatureExtractor) last extract,
+        on host slot ``slot``; x / y go device to device.  Returns the number added."""
+        n = C.c_int()
+        check(self.lib.hs_tracer_add_keys(self.h, extractor.h, int(slot), C.byref(n)))
+        self.n += n.value
+        return n.value
+
     def set_state(self, idepth_min=None, idepth_max=None, quality=None, status=None, interval=None):
         arr = [None if a is None else np.ascontiguousarray(a, dt)
                for a, dt in ((idepth_min, np.float32), (idepth_max, np.float32), (quality, np.float32),

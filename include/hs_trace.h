@@ -54,6 +54,8 @@ void hs_tracer_destroy(hs_tracer* t);
 int hs_tracer_set_host_image(hs_tracer* t, int slot, const float* img_lvl0);
 /* ImmaturePoint ctor for n new points on host slots host[i] at (u[i], v[i]); appended after existing points */
 int hs_tracer_add_points(hs_tracer* t, int n, const int* host, const float* u, const float* v);
+/* the same for every key of an extractor's last extract, device to device: hs_tracer_add_keys, declared in
+   hs_extract.h beside the extractor it reads */
 /* drop all points (a new window) */
 int hs_tracer_clear(hs_tracer* t);
 /* overwrite the search state of all points (nullable arrays of length n_points): a point traced before;
