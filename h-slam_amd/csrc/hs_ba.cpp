@@ -26,6 +26,7 @@ using namespace hs;
 
 namespace hs {
 thread_local std::string g_err;  // hs_last_error(), shared by every entry point of the library
+std::atomic<long long> g_live{0};  // hs_debug_live_allocations()
 }
 
 namespace hs {
@@ -51,52 +52,9 @@ int max_blocks_for(int capP) {
 
 static void free_buffers(hs_ctx* c) {
   drop_graph(c);
-  std::vector<void*> ptrs = {
-      c->d_img_all, c->d_img3, c->d_raw, c->d_state, c->d_pre, c->d_frameTH, c->d_res_of_slot, c->d_pt_host,
-      c->d_host_pt_begin, c->d_res_order, c->d_r_active, c->d_r_energy, c->d_r_newEnergy, c->d_r_ewo,
-      c->d_p_actmask, c->d_p_HdiF, c->d_p_bdSumF, c->d_p_Hcd, c->d_p_JpJdF, c->d_p_step, c->d_part, c->d_part_e,
-      c->d_hostsum, c->d_sys, c->d_sep, c->d_adHost, c->d_adTarget, c->d_adHostF, c->d_adTargetF, c->d_HM, c->d_bM,
-      c->d_Nproj, c->d_xAd, c->d_x, c->d_elog, c->d_cand, c->d_tr_lin, c->d_tr_acc, c->d_tr_solve, c->d_tr_st,
-      c->d_marg, c->d_adHTdelta, c->d_p_HdiF_alt, c->d_th_hist, c->d_th_hist2, c->d_th_surv, c->d_th_nsurv,
-      c->d_le_chunk, c->d_le_out, c->d_ref_pts, c->d_ref_n, c->d_stage, c->d_gsys, c->d_sep_aux, c->d_ticket};
-  for (auto& s : c->ps) {
-    for (void* p : {(void*)s.u, (void*)s.v, (void*)s.idepth, (void*)s.idepth_zero, (void*)s.priorF, (void*)s.color,
-                    (void*)s.weight, (void*)s.relBL, (void*)s.nGood, (void*)s.r_state, (void*)s.r_center})
-      ptrs.push_back(p);
-    s = PointSet();
-  }
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  if (c->h_raw) (void)hipHostFree(c->h_raw);
-  c->h_stage = nullptr;
-  c->h_stage_cap = 0;
-  c->h_raw = nullptr;
-  c->d_img_all = nullptr; c->d_img3 = nullptr; c->d_raw = nullptr;
-  c->d_state = nullptr; c->d_pre = nullptr; c->d_frameTH = nullptr;
-  c->d_res_of_slot = c->d_pt_host = c->d_host_pt_begin = nullptr;
-  c->d_res_order = nullptr;
-  c->d_r_active = nullptr;
-  c->d_r_energy = c->d_r_newEnergy = c->d_r_ewo = nullptr;
-  c->d_p_actmask = nullptr;
-  c->d_p_HdiF = c->d_p_bdSumF = c->d_p_Hcd = c->d_p_JpJdF = c->d_p_step = nullptr;
-  c->d_part = nullptr; c->d_part_e = nullptr; c->d_hostsum = nullptr; c->d_sys = nullptr; c->d_sep = nullptr;
-  c->d_adHost = c->d_adTarget = nullptr; c->d_adHostF = c->d_adTargetF = nullptr;
-  c->d_HM = c->d_bM = c->d_Nproj = nullptr;
-  c->d_xAd = nullptr; c->d_x = nullptr; c->d_elog = nullptr; c->d_cand = nullptr;
-  c->d_tr_lin = c->d_tr_acc = c->d_tr_solve = c->d_tr_st = nullptr;
-  c->d_marg = nullptr;
-  c->d_adHTdelta = nullptr;
-  c->d_p_HdiF_alt = nullptr;
+  c->cap.release_all();  // nulls every slot it frees
   c->hdif_solved = nullptr;
-  c->d_th_hist = nullptr;
-  c->d_th_hist2 = c->d_th_surv = c->d_th_nsurv = nullptr;
-  c->d_le_chunk = nullptr; c->d_le_out = nullptr;
-  c->d_ref_pts = nullptr; c->d_ref_n = nullptr;
-  c->d_stage = nullptr;
-  c->d_gsys = nullptr;
-  c->d_sep_aux = nullptr;
-  c->d_ticket = nullptr;
+  c->h_stage_cap = 0;
   c->gath_pending = false;
   c->gath_th = 0;
   c->d_stage_cap = 0;
@@ -169,16 +127,15 @@ int cand_stride_for(hs_ctx* c, int nP, int* stride) {
     if (s > c->group_stride) return fail(HS_ERR_INVALID, "shard exceeds the group's candidate stride");
     s = c->group_stride;
   } else if (c->comm) {
+    hs::Pool scratch;  // freed on every return path
     int* d_tmp = nullptr;
-    HS_TRY(dalloc(&d_tmp, 1, c->stream));
+    HS_TRY(scratch.alloc_zero(&d_tmp, 1, c->stream));
     // every step on the context's stream (a null-stream copy would not order against it); h_ctl[6]: pinned scratch
     c->h_ctl[6] = s;
     HS_HIP(hipMemcpyAsync(d_tmp, &c->h_ctl[6], sizeof(int), hipMemcpyHostToDevice, c->stream));
     HS_NCCL(ncclAllReduce(d_tmp, d_tmp, 1, ncclInt, ncclMax, c->comm, c->stream));
     HS_HIP(hipMemcpyAsync(&c->h_ctl[6], d_tmp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    const int rc = wait_stream(c);
-    (void)hipFree(d_tmp);
-    if (rc != HS_OK) return rc;
+    HS_TRY(wait_stream(c));
     s = c->h_ctl[6];
   }
   *stride = s;
@@ -194,73 +151,75 @@ int ensure_capacity(hs_ctx* c, int W, int H, int capP, int capBlk) {
   if (c->d_state && W == c->cap_W && H == c->cap_H && capP <= c->cap_P && capBlk <= c->cap_blk) return HS_OK;
   HS_TRY(wait_stream(c));
   free_buffers(c);
+  // zero-filled on the context's stream (Pool::alloc_zero)
+  auto dalloc = [c](auto** p, size_t n) { return c->cap.alloc_zero(p, n, c->stream); };
   const size_t npx = (size_t)W * H, P8 = (size_t)capP * 8;
   const int nmax = HS_MAXDIM, SLmax = nmax * nmax + nmax, ne = hs_ne(true), FF = HS_MAXF * HS_MAXF;
-  HS_TRY(dalloc(&c->d_img_all, npx * HS_MAXF, c->stream));
-  HS_TRY(dalloc(&c->d_img3, npx * HS_MAXF * 3, c->stream));
+  HS_TRY(dalloc(&c->d_img_all, npx * HS_MAXF));
+  HS_TRY(dalloc(&c->d_img3, npx * HS_MAXF * 3));
   c->img_px = npx;
-  HS_TRY(dalloc(&c->d_state, 1, c->stream));
-  HS_TRY(dalloc(&c->d_pre, FF, c->stream));
-  HS_TRY(dalloc(&c->d_frameTH, HS_MAXF, c->stream));
+  HS_TRY(dalloc(&c->d_state, 1));
+  HS_TRY(dalloc(&c->d_pre, FF));
+  HS_TRY(dalloc(&c->d_frameTH, HS_MAXF));
   for (auto& s : c->ps) {
-    HS_TRY(dalloc(&s.u, capP, c->stream)); HS_TRY(dalloc(&s.v, capP, c->stream));
-    HS_TRY(dalloc(&s.idepth, capP, c->stream)); HS_TRY(dalloc(&s.idepth_zero, capP, c->stream)); HS_TRY(dalloc(&s.priorF, capP, c->stream));
-    HS_TRY(dalloc(&s.color, P8, c->stream)); HS_TRY(dalloc(&s.weight, P8, c->stream));
-    HS_TRY(dalloc(&s.relBL, capP, c->stream)); HS_TRY(dalloc(&s.nGood, capP, c->stream));
-    HS_TRY(dalloc(&s.r_state, P8, c->stream)); HS_TRY(dalloc(&s.r_center, P8 * 3, c->stream));
+    HS_TRY(dalloc(&s.u, capP)); HS_TRY(dalloc(&s.v, capP));
+    HS_TRY(dalloc(&s.idepth, capP)); HS_TRY(dalloc(&s.idepth_zero, capP)); HS_TRY(dalloc(&s.priorF, capP));
+    HS_TRY(dalloc(&s.color, P8)); HS_TRY(dalloc(&s.weight, P8));
+    HS_TRY(dalloc(&s.relBL, capP)); HS_TRY(dalloc(&s.nGood, capP));
+    HS_TRY(dalloc(&s.r_state, P8)); HS_TRY(dalloc(&s.r_center, P8 * 3));
   }
   c->cur = 0;
-  HS_TRY(dalloc(&c->d_res_of_slot, P8, c->stream)); HS_TRY(dalloc(&c->d_res_order, P8, c->stream));
-  HS_TRY(dalloc(&c->d_pt_host, capP, c->stream)); HS_TRY(dalloc(&c->d_host_pt_begin, HS_MAXF + 1, c->stream));
+  HS_TRY(dalloc(&c->d_res_of_slot, P8)); HS_TRY(dalloc(&c->d_res_order, P8));
+  HS_TRY(dalloc(&c->d_pt_host, capP)); HS_TRY(dalloc(&c->d_host_pt_begin, HS_MAXF + 1));
   // residual state in the slot layout [point][target slot] (P8 entries; slots without a residual unused)
-  HS_TRY(dalloc(&c->d_r_active, P8, c->stream));
-  HS_TRY(dalloc(&c->d_r_energy, P8, c->stream)); HS_TRY(dalloc(&c->d_r_newEnergy, P8, c->stream)); HS_TRY(dalloc(&c->d_r_ewo, P8, c->stream));
-  HS_TRY(dalloc(&c->d_p_actmask, capP, c->stream)); HS_TRY(dalloc(&c->d_p_HdiF, capP, c->stream)); HS_TRY(dalloc(&c->d_p_bdSumF, capP, c->stream));
-  HS_TRY(dalloc(&c->d_p_Hcd, (size_t)capP * 4, c->stream)); HS_TRY(dalloc(&c->d_p_JpJdF, P8 * 8, c->stream));
-  HS_TRY(dalloc(&c->d_p_step, capP, c->stream)); HS_TRY(dalloc(&c->d_p_HdiF_alt, capP, c->stream));
+  HS_TRY(dalloc(&c->d_r_active, P8));
+  HS_TRY(dalloc(&c->d_r_energy, P8)); HS_TRY(dalloc(&c->d_r_newEnergy, P8)); HS_TRY(dalloc(&c->d_r_ewo, P8));
+  HS_TRY(dalloc(&c->d_p_actmask, capP)); HS_TRY(dalloc(&c->d_p_HdiF, capP)); HS_TRY(dalloc(&c->d_p_bdSumF, capP));
+  HS_TRY(dalloc(&c->d_p_Hcd, (size_t)capP * 4)); HS_TRY(dalloc(&c->d_p_JpJdF, P8 * 8));
+  HS_TRY(dalloc(&c->d_p_step, capP)); HS_TRY(dalloc(&c->d_p_HdiF_alt, capP));
   c->hdif_solved = c->d_p_HdiF;
-  HS_TRY(dalloc(&c->d_part, (size_t)capBlk * ne * 64, c->stream));
-  HS_TRY(dalloc(&c->d_part_e, (size_t)capBlk * 4, c->stream));
-  HS_TRY(dalloc(&c->d_hostsum, (size_t)HS_MAXF * ne * 64, c->stream));
-  HS_TRY(dalloc(&c->d_sys, (size_t)SLmax + 3 + HS_MAXF * 64, c->stream));
-  HS_TRY(dalloc(&c->d_sep, (size_t)2 * SLmax, c->stream));
-  HS_TRY(dalloc(&c->d_sep_aux, (size_t)HS_MAXF * 64, c->stream));
+  HS_TRY(dalloc(&c->d_part, (size_t)capBlk * ne * 64));
+  HS_TRY(dalloc(&c->d_part_e, (size_t)capBlk * 4));
+  HS_TRY(dalloc(&c->d_hostsum, (size_t)HS_MAXF * ne * 64));
+  HS_TRY(dalloc(&c->d_sys, (size_t)SLmax + 3 + HS_MAXF * 64));
+  HS_TRY(dalloc(&c->d_sep, (size_t)2 * SLmax));
+  HS_TRY(dalloc(&c->d_sep_aux, (size_t)HS_MAXF * 64));
   // the adjoints + one stamp word each (HS_ADJ_STAMP: hs_k_fix_frames' upload sequence, checked by their readers)
-  HS_TRY(dalloc(&c->d_adHost, FF * 64 + 1, c->stream)); HS_TRY(dalloc(&c->d_adTarget, FF * 64 + 1, c->stream));
-  HS_TRY(dalloc(&c->d_adHostF, FF * 64 + 1, c->stream)); HS_TRY(dalloc(&c->d_adTargetF, FF * 64 + 1, c->stream));
-  HS_TRY(dalloc(&c->d_HM, (size_t)nmax * nmax, c->stream)); HS_TRY(dalloc(&c->d_bM, nmax, c->stream));
-  HS_TRY(dalloc(&c->d_Nproj, (size_t)2 * nmax * HS_NNS, c->stream));
-  HS_TRY(dalloc(&c->d_xAd, FF * 8, c->stream)); HS_TRY(dalloc(&c->d_x, nmax, c->stream)); HS_TRY(dalloc(&c->d_elog, kLogCap, c->stream));
+  HS_TRY(dalloc(&c->d_adHost, FF * 64 + 1)); HS_TRY(dalloc(&c->d_adTarget, FF * 64 + 1));
+  HS_TRY(dalloc(&c->d_adHostF, FF * 64 + 1)); HS_TRY(dalloc(&c->d_adTargetF, FF * 64 + 1));
+  HS_TRY(dalloc(&c->d_HM, (size_t)nmax * nmax)); HS_TRY(dalloc(&c->d_bM, nmax));
+  HS_TRY(dalloc(&c->d_Nproj, (size_t)2 * nmax * HS_NNS));
+  HS_TRY(dalloc(&c->d_xAd, FF * 8)); HS_TRY(dalloc(&c->d_x, nmax)); HS_TRY(dalloc(&c->d_elog, kLogCap));
   int stride = capP;
   HS_TRY(cand_stride_for(c, capP, &stride));
   c->cap_stride = stride;
-  HS_TRY(dalloc(&c->d_cand, (size_t)stride * c->nranks, c->stream));
+  HS_TRY(dalloc(&c->d_cand, (size_t)stride * c->nranks));
   HS_HIP(hipMemsetAsync(c->d_cand, 0xff, sizeof(float) * (size_t)stride * c->nranks, c->stream));  // NaN: none
-  if (c->multi_rank()) HS_TRY(dalloc(&c->d_gsys, ((size_t)SLmax + 3 + HS_MAXF * 64) * c->nranks, c->stream));
-  HS_TRY(dalloc(&c->d_th_hist, HS_TH_BINS, c->stream));
-  HS_TRY(dalloc(&c->d_th_hist2, 1024, c->stream));
-  HS_TRY(dalloc(&c->d_th_nsurv, 2, c->stream));
-  HS_TRY(dalloc(&c->d_th_surv, HS_TH_SURV, c->stream));
-  HS_TRY(dalloc(&c->d_marg, capP, c->stream));
-  HS_TRY(dalloc(&c->d_adHTdelta, FF * 8 + 4, c->stream));  // + cDeltaF
-  HS_TRY(dalloc(&c->d_le_chunk, (size_t)(capP + 49) / 50, c->stream));
-  HS_TRY(dalloc(&c->d_le_out, 1, c->stream));
-  HS_TRY(dalloc(&c->d_ref_pts, (size_t)4 * capP, c->stream));
-  HS_TRY(dalloc(&c->d_ref_n, 1, c->stream));
-  HS_TRY(dalloc(&c->d_ticket, 2, c->stream));  // [0] the stitch's retire ticket, [1] the adjoint expectation
+  if (c->multi_rank()) HS_TRY(dalloc(&c->d_gsys, ((size_t)SLmax + 3 + HS_MAXF * 64) * c->nranks));
+  HS_TRY(dalloc(&c->d_th_hist, HS_TH_BINS));
+  HS_TRY(dalloc(&c->d_th_hist2, 1024));
+  HS_TRY(dalloc(&c->d_th_nsurv, 2));
+  HS_TRY(dalloc(&c->d_th_surv, HS_TH_SURV));
+  HS_TRY(dalloc(&c->d_marg, capP));
+  HS_TRY(dalloc(&c->d_adHTdelta, FF * 8 + 4));  // + cDeltaF
+  HS_TRY(dalloc(&c->d_le_chunk, (size_t)(capP + 49) / 50));
+  HS_TRY(dalloc(&c->d_le_out, 1));
+  HS_TRY(dalloc(&c->d_ref_pts, (size_t)4 * capP));
+  HS_TRY(dalloc(&c->d_ref_n, 1));
+  HS_TRY(dalloc(&c->d_ticket, 2));  // [0] the stitch's retire ticket, [1] the adjoint expectation
   // incremental window: the commit blob (pinned + device) and a raw level-0 image's staging
   c->h_stage_cap = c->d_stage_cap = stage_bytes(capP);
-  HS_HIP(hipHostMalloc((void**)&c->h_stage, c->h_stage_cap));
-  HS_TRY(dalloc(&c->d_stage, c->d_stage_cap, c->stream));
-  HS_HIP(hipHostMalloc((void**)&c->h_raw, sizeof(float) * npx));
-  HS_TRY(dalloc(&c->d_raw, npx, c->stream));
+  HS_TRY(c->cap.pinned(&c->h_stage, c->h_stage_cap));
+  HS_TRY(dalloc(&c->d_stage, c->d_stage_cap));
+  HS_TRY(c->cap.pinned(&c->h_raw, npx));
+  HS_TRY(dalloc(&c->d_raw, npx));
   const char* tr = std::getenv("HS_KTRACE");
   c->tracing = tr && tr[0] == '1';
   if (c->tracing) {
-    HS_TRY(dalloc(&c->d_tr_lin, (size_t)capBlk * 16, c->stream));
-    HS_TRY(dalloc(&c->d_tr_acc, (size_t)(HS_MAXF * ((ne * 64 + 255) / 256) + 1 + 64) * 16, c->stream));
-    HS_TRY(dalloc(&c->d_tr_st, (size_t)(HS_MAXF * (HS_MAXF + 1) / 2 + 2 * HS_MAXF + 2 + 64) * 16, c->stream));  // + np2 <= 64
-    HS_TRY(dalloc(&c->d_tr_solve, 32, c->stream));
+    HS_TRY(dalloc(&c->d_tr_lin, (size_t)capBlk * 16));
+    HS_TRY(dalloc(&c->d_tr_acc, (size_t)(HS_MAXF * ((ne * 64 + 255) / 256) + 1 + 64) * 16));
+    HS_TRY(dalloc(&c->d_tr_st, (size_t)(HS_MAXF * (HS_MAXF + 1) / 2 + 2 * HS_MAXF + 2 + 64) * 16));  // + np2 <= 64
+    HS_TRY(dalloc(&c->d_tr_solve, 32));
   }
   c->cap_W = W; c->cap_H = H; c->cap_P = capP; c->cap_blk = capBlk;
   bind_point_set(c);
@@ -1111,31 +1070,28 @@ const char* hs_last_error(void) { return g_err.c_str(); }
 int hs_create(hs_ctx** out, const hs_params* params, int device_id) {
   if (!out) return fail(HS_ERR_INVALID, "null out");
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(HS_ERR_HIP, "no HIP device");
-  if (device_id < 0 || device_id >= ndev) return fail(HS_ERR_INVALID, "bad device id");
+  HS_TRY(check_device(device_id));
   hs_ctx* c = new hs_ctx();
   if (params) c->P = *params;
   else hs_params_default(&c->P);
-  c->device = device_id;
   const char* ev = std::getenv("HS_EVENT_TIMING");
   c->events = ev ? std::atoi(ev) : 0;
-  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_state, sizeof(HsDevState)) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_ctl, 8 * sizeof(int)) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_res, sizeof(double) * (kLogCap + 3), hipHostMallocMapped | hipHostMallocCoherent) !=
-          hipSuccess ||
-      hipHostGetDevicePointer((void**)&c->d_res, c->h_res, 0) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_fstage, fstage_bytes() + 256) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming) != hipSuccess) {
-    delete c;
-    return fail(HS_ERR_HIP, "stream / pinned allocation failed");
-  }
-  c->ev.assign(4 * kEventIters, nullptr);
-  for (auto& e : c->ev) HS_HIP(hipEventCreate(&e));
-  *out = c;
-  return HS_OK;
+  const int rc = [&]() -> int {
+    HS_TRY(c->open(device_id));
+    HS_TRY(c->pool.pinned(&c->h_state, 1));
+    HS_TRY(c->pool.pinned(&c->h_ctl, 8));
+    HS_TRY(c->pool.pinned(&c->h_res, kLogCap + 3, hipHostMallocMapped | hipHostMallocCoherent));
+    HS_HIP(hipHostGetDevicePointer((void**)&c->d_res, c->h_res, 0));
+    HS_TRY(c->pool.pinned(&c->h_fstage, fstage_bytes() + 256));
+    HS_HIP(hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming));
+    HS_HIP(hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming));
+    c->ev.assign(4 * kEventIters, nullptr);
+    for (auto& e : c->ev) HS_HIP(hipEventCreate(&e));
+    return HS_OK;
+  }();
+  if (rc) hs_destroy(c);
+  else *out = c;
+  return rc;
 }
 
 void hs_destroy(hs_ctx* c) {
@@ -1144,21 +1100,17 @@ void hs_destroy(hs_ctx* c) {
   if (c->abort_thread.joinable()) c->abort_thread.join();  // an aborted communicator (comm_fail)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   free_buffers(c);
+  c->pool.release_all();
   if (c->comm) ncclCommDestroy(c->comm);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
-  if (c->h_state) (void)hipHostFree(c->h_state);
-  if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-  if (c->h_res) (void)hipHostFree(c->h_res);
-  if (c->h_rb) (void)hipHostFree(c->h_rb);
-  if (c->h_fstage) (void)hipHostFree(c->h_fstage);
   if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
   if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
   for (auto& e : c->ev_xch)
     if (e) (void)hipEventDestroy(e);
   for (hs_ctx* p : c->group)  // a destroyed member leaves its group (the others can no longer exchange)
     if (p != c) p->group.clear();
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  c->close();
   delete c;
 }
 
@@ -1297,8 +1249,7 @@ int hs_ba_set_window(hs_ctx* c, const hs_camera* cam, int nF, const hs_frame* fr
   const size_t npx = (size_t)cam->width * cam->height;
   std::vector<float4> tex(npx);
   for (int f = 0; f < nF; f++) {
-    const float* src = images[f];
-    for (size_t i = 0; i < npx; i++) tex[i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0.f);
+    texels_from_triplets(tex.data(), images[f], npx);
     HS_HIP(hipMemcpyAsync(c->d_img_all + (size_t)f * npx, tex.data(), npx * sizeof(float4), hipMemcpyHostToDevice,
                           c->stream));
     HS_TRY(wait_stream(c));  // tex is reused
@@ -1444,7 +1395,7 @@ int hs_ba_fix_linearization(hs_ctx* c, double* energy_out, uint8_t* drop_out, fl
   HS_HIP(hipSetDevice(c->device));
   const int nP = c->nP;
   // pinned staging of the read-backs: HdiF [nP] floats, then the active flags [nP][8]; one sync for all of them
-  HS_HIP(c->rb_stage(sizeof(float) * (size_t)nP + (size_t)nP * 8));
+  HS_TRY(c->rb_stage(sizeof(float) * (size_t)nP + (size_t)nP * 8));
   c->rb_pending = true;  // cleared after the stream sync below; an early return leaves it for the next rb_stage
   float* h_hdif = reinterpret_cast<float*>(c->h_rb);
   unsigned char* h_act = c->h_rb + sizeof(float) * (size_t)nP;
@@ -1709,7 +1660,7 @@ int hs_ba_marginalize_points(hs_ctx* c, int n, const int* points, double* HM_out
   }
   // EnergyFunctional::setDeltaF (Src/EnergyFunctional.cpp:128-152) from the device state, in fp32 (hs_k_marg_delta);
   // the flags through the pinned staging, asynchronous (rb_pending: the next rb_stage waits for the copy)
-  HS_HIP(c->rb_stage((size_t)c->nP + 1));
+  HS_TRY(c->rb_stage((size_t)c->nP + 1));
   c->rb_pending = true;
   std::memcpy(c->h_rb, flag.data(), (size_t)c->nP);
   if (c->nP > 0) HS_HIP(hipMemcpyAsync(c->d_marg, c->h_rb, c->nP, hipMemcpyHostToDevice, c->stream));
@@ -2023,8 +1974,10 @@ extern "C" int hs_debug_threshold(const float* cand, int n, float thn, float fac
   float *d_c = nullptr, *d_th = nullptr;
   unsigned int *d_h = nullptr, *d_h2 = nullptr, *d_surv = nullptr, *d_ns = nullptr;
   double* d_e = nullptr;
-  HS_TRY(dalloc(&d_c, n, nullptr)); HS_TRY(dalloc(&d_th, 1, nullptr)); HS_TRY(dalloc(&d_h, HS_TH_BINS, nullptr)); HS_TRY(dalloc(&d_e, 4, nullptr));
-  HS_TRY(dalloc(&d_h2, 1024, nullptr)); HS_TRY(dalloc(&d_surv, HS_TH_SURV, nullptr)); HS_TRY(dalloc(&d_ns, 2, nullptr));
+  Pool scratch;  // freed on every return path
+  auto dalloc = [&](auto** p, size_t m) { return scratch.alloc_zero(p, m, nullptr); };
+  HS_TRY(dalloc(&d_c, n)); HS_TRY(dalloc(&d_th, 1)); HS_TRY(dalloc(&d_h, HS_TH_BINS)); HS_TRY(dalloc(&d_e, 4));
+  HS_TRY(dalloc(&d_h2, 1024)); HS_TRY(dalloc(&d_surv, HS_TH_SURV)); HS_TRY(dalloc(&d_ns, 2));
   HS_HIP(hipMemcpy(d_c, cand, sizeof(float) * n, hipMemcpyHostToDevice));
   HsRedArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -2055,8 +2008,7 @@ extern "C" int hs_debug_threshold(const float* cand, int n, float thn, float fac
   HS_HIP(hipMemcpy(hz.data(), d_h, sizeof(unsigned int) * HS_TH_BINS, hipMemcpyDeviceToHost));
   HS_HIP(hipMemcpy(h2.data(), d_h2, sizeof(unsigned int) * 1024, hipMemcpyDeviceToHost));
   HS_HIP(hipMemcpy(ns.data(), d_ns, sizeof(unsigned int) * 2, hipMemcpyDeviceToHost));
-  for (void* p : {(void*)d_c, (void*)d_th, (void*)d_h, (void*)d_e, (void*)d_h2, (void*)d_surv, (void*)d_ns})
-    (void)hipFree(p);
+  scratch.release_all();
   for (unsigned int v : hz)
     if (v) return fail(HS_ERR_STATE, "threshold histogram not re-zeroed");
   for (unsigned int v : h2)
@@ -2088,14 +2040,13 @@ extern "C" int hs_debug_se3(int on_device, int op, int n, const double* in14, do
     return HS_OK;
   }
   double *d_in = nullptr, *d_out = nullptr;
-  HS_TRY(dalloc(&d_in, (size_t)14 * n, nullptr));
-  HS_TRY(dalloc(&d_out, (size_t)36 * n, nullptr));
+  Pool scratch;  // freed on every return path
+  HS_TRY(scratch.alloc_zero(&d_in, (size_t)14 * n, nullptr));
+  HS_TRY(scratch.alloc_zero(&d_out, (size_t)36 * n, nullptr));
   HS_HIP(hipMemcpy(d_in, in14, sizeof(double) * 14 * n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(hs_k_debug_se3, dim3((n + 63) / 64), dim3(64), 0, 0, op, n, d_in, d_out);
   HS_HIP(hipGetLastError());
   HS_HIP(hipMemcpy(out36, d_out, sizeof(double) * 36 * n, hipMemcpyDeviceToHost));
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
   return HS_OK;
 }
 
@@ -2103,17 +2054,15 @@ extern "C" int hs_debug_se3(int on_device, int op, int n, const double* in14, do
 extern "C" int hs_debug_fastmath(int n, const float* a, const float* b, float* out4) {
   if (n < 1 || !a || !b || !out4) return fail(HS_ERR_INVALID, "bad arguments");
   float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
-  HS_TRY(dalloc(&d_a, (size_t)n, nullptr));
-  HS_TRY(dalloc(&d_b, (size_t)n, nullptr));
-  HS_TRY(dalloc(&d_o, (size_t)4 * n, nullptr));
+  Pool scratch;  // freed on every return path
+  HS_TRY(scratch.alloc_zero(&d_a, (size_t)n, nullptr));
+  HS_TRY(scratch.alloc_zero(&d_b, (size_t)n, nullptr));
+  HS_TRY(scratch.alloc_zero(&d_o, (size_t)4 * n, nullptr));
   HS_HIP(hipMemcpy(d_a, a, sizeof(float) * n, hipMemcpyHostToDevice));
   HS_HIP(hipMemcpy(d_b, b, sizeof(float) * n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(hs_k_debug_fastmath, dim3((n + 255) / 256), dim3(256), 0, 0, n, d_a, d_b, d_o);
   HS_HIP(hipGetLastError());
   HS_HIP(hipMemcpy(out4, d_o, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
-  (void)hipFree(d_a);
-  (void)hipFree(d_b);
-  (void)hipFree(d_o);
   return HS_OK;
 }
 
@@ -2154,13 +2103,15 @@ extern "C" int hs_debug_stitch(int nF, int exact, const double* hostsum, const d
   if (nF < 1 || nF > HS_MAXF || !hostsum || !adH || !adT || !out) return fail(HS_ERR_INVALID, "bad args");
   const int n = 4 + 8 * nF, SL = n * n + n, ne = hs_ne(exact != 0);
   double *dh = nullptr, *da = nullptr, *dt = nullptr, *dout = nullptr, *dsep = nullptr, *dax = nullptr, *dax2 = nullptr;
-  HS_TRY(dalloc(&dax, (size_t)nF * 64, nullptr));
-  HS_TRY(dalloc(&dax2, (size_t)nF * 64, nullptr));
-  HS_TRY(dalloc(&dh, (size_t)nF * ne * 64, nullptr));
-  HS_TRY(dalloc(&da, (size_t)nF * nF * 64, nullptr));
-  HS_TRY(dalloc(&dt, (size_t)nF * nF * 64, nullptr));
-  HS_TRY(dalloc(&dout, (size_t)SL, nullptr));
-  HS_TRY(dalloc(&dsep, (size_t)2 * SL, nullptr));
+  Pool scratch;  // freed on every return path
+  auto dalloc = [&](double** p, size_t m) { return scratch.alloc_zero(p, m, nullptr); };
+  HS_TRY(dalloc(&dax, (size_t)nF * 64));
+  HS_TRY(dalloc(&dax2, (size_t)nF * 64));
+  HS_TRY(dalloc(&dh, (size_t)nF * ne * 64));
+  HS_TRY(dalloc(&da, (size_t)nF * nF * 64));
+  HS_TRY(dalloc(&dt, (size_t)nF * nF * 64));
+  HS_TRY(dalloc(&dout, (size_t)SL));
+  HS_TRY(dalloc(&dsep, (size_t)2 * SL));
   HS_HIP(hipMemcpy(dh, hostsum, sizeof(double) * nF * ne * 64, hipMemcpyHostToDevice));
   HS_HIP(hipMemcpy(da, adH, sizeof(double) * nF * nF * 64, hipMemcpyHostToDevice));
   HS_HIP(hipMemcpy(dt, adT, sizeof(double) * nF * nF * 64, hipMemcpyHostToDevice));
@@ -2180,7 +2131,7 @@ extern "C" int hs_debug_stitch(int nF, int exact, const double* hostsum, const d
   std::vector<double> ax((size_t)nF * 64), ax2((size_t)nF * 64);
   HS_HIP(hipMemcpy(ax.data(), dax, sizeof(double) * ax.size(), hipMemcpyDeviceToHost));
   HS_HIP(hipMemcpy(ax2.data(), dax2, sizeof(double) * ax2.size(), hipMemcpyDeviceToHost));
-  for (double* p : {dh, da, dt, dout, dsep, dax, dax2}) (void)hipFree(p);
+  scratch.release_all();
   // the consumers' fold of the diagonal blocks' host-f Schur terms
   for (int f = 0; f < nF; f++)
     for (int i = 0; i < 8; i++)
@@ -2214,3 +2165,7 @@ extern "C" int hs_debug_stall(hs_ctx* c, int ms) {
 
 // test hook (not in the header, no device work): whether a W x H window may run hs_k_lin8 (lin8_supported)
 extern "C" int hs_debug_lin8_supported(int W, int H) { return hs::lin8_supported(W, H) ? 1 : 0; }
+
+// test hook (not in the header, no device work): device and pinned allocations every hs::Pool of the process has
+// handed out and not yet freed
+extern "C" long long hs_debug_live_allocations(void) { return hs::g_live.load(); }

@@ -4,7 +4,6 @@
 // whole-window set-up, read-back), hs_ba_window.cpp (insert / drop / remove / commit) and hs_track.cpp (the
 // BA -> tracker hand-off of makeCoarseDepthL0's inputs).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <cstdint>
@@ -13,34 +12,15 @@
 #include <vector>
 
 #include "../../include/hs_ba.h"
+#include "hs_host.h"
 #include "hs_host_math.h"
 #include "hs_kernels.h"
 #include "hs_win_kernels.h"
-
-namespace hs {
-extern thread_local std::string g_err;  // hs_last_error(), shared by every entry point of the library
-inline int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-}  // namespace hs
-
-#define HS_HIP(x)                                                                                          \
-  do {                                                                                                     \
-    hipError_t e_ = (x);                                                                                   \
-    if (e_ != hipSuccess) return hs::fail(HS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
 #define HS_NCCL(x)                                                                                            \
   do {                                                                                                        \
     ncclResult_t r_ = (x);                                                                                    \
     if (r_ != ncclSuccess) return hs::fail(HS_ERR_RCCL, std::string(#x) + ": " + ncclGetErrorString(r_));     \
-  } while (0)
-
-#define HS_TRY(x)        \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
   } while (0)
 
 namespace hs {
@@ -61,17 +41,6 @@ constexpr int kLin8BlocksTarget = 256;  // hs_k_lin8 blocks of a window (one 8-w
 inline bool lin8_supported(int W, int H) {
   const long long px = (long long)W * H;
   return px < (1LL << 23) && (long long)HS_MAXF * px * 12 + 12 * (long long)W <= 0x7fffffffLL;
-}
-
-// Allocate and zero-fill n elements; the fill is enqueued on `s`, the stream every later user of the buffer runs on.
-// (A null-stream hipMemset returns before the fill lands and does not order against a hipStreamNonBlocking stream:
-// a context's first kernel could store into a buffer that the fill then zeroed -- tools/micro/memset_order.hip.)
-template <typename T>
-inline int dalloc(T** p, size_t n, hipStream_t s) {
-  if (n == 0) n = 1;
-  HS_HIP(hipMalloc((void**)p, n * sizeof(T)));
-  HS_HIP(hipMemsetAsync(*p, 0, n * sizeof(T), s));
-  return HS_OK;
 }
 
 // Per-point state that survives a structural commit (double-buffered: the commit gathers set A into set B in the new
@@ -102,10 +71,10 @@ struct WinPoint {
 
 }  // namespace hs
 
-struct hs_ctx {
+struct hs_ctx : hs::Device {
   hs_params P;
-  int device = 0;
-  hipStream_t stream = nullptr;
+  hs::Pool pool;  // the context's lifetime: h_state, h_ctl, h_res, h_fstage, h_rb
+  hs::Pool cap;   // the capacity set: what ensure_capacity allocates and a larger window replaces
   std::vector<hipEvent_t> ev;  // 4 per timed iteration
   hipEvent_t ev_ready = nullptr;  // cross-stream hand-off (BA -> tracker)
   hipEvent_t ev_upload = nullptr; // the last asynchronous upload from the pinned staging buffers (h_fstage, h_stage,
@@ -263,19 +232,16 @@ struct hs_ctx {
   unsigned char* h_rb = nullptr;
   size_t h_rb_cap = 0;
   bool rb_pending = false;  // an asynchronous copy from / into h_rb may still be in flight (a call left early)
-  hipError_t rb_stage(size_t bytes) {
+  int rb_stage(size_t bytes) {
     if (rb_pending) {  // the last user returned before its stream sync (an error path): drain before reuse
-      const hipError_t e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) return e;
+      HS_HIP(hipStreamSynchronize(stream));
       rb_pending = false;
     }
-    if (bytes <= h_rb_cap) return hipSuccess;
-    if (h_rb) (void)hipHostFree(h_rb);
-    h_rb = nullptr;
+    if (bytes <= h_rb_cap) return HS_OK;
     h_rb_cap = 0;
-    const hipError_t e = hipHostMalloc((void**)&h_rb, bytes);
-    if (e == hipSuccess) h_rb_cap = bytes;
-    return e;
+    HS_TRY(pool.pinned(&h_rb, bytes));
+    h_rb_cap = bytes;
+    return HS_OK;
   }
   double* h_res = nullptr;
   double* d_res = nullptr;  // the device view of h_res

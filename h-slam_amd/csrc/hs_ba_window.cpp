@@ -402,7 +402,7 @@ int hs_ba_set_frame_image(hs_ctx* c, int frame, const float* image) {
   // (I, dI/dx, dI/dy) triplets -> float4 texels on the host, one synchronous copy (the host-image path; the raw and
   // device paths below avoid both)
   std::vector<float4> tex(c->img_px);
-  for (size_t i = 0; i < c->img_px; i++) tex[i] = make_float4(image[3 * i], image[3 * i + 1], image[3 * i + 2], 0.f);
+  texels_from_triplets(tex.data(), image, c->img_px);
   HS_HIP(hipMemcpyAsync(dst, tex.data(), c->img_px * sizeof(float4), hipMemcpyHostToDevice, c->stream));
   HS_TRY(pack_slot(c, c->wframes[frame].slot));
   HS_TRY(wait_stream(c));
@@ -544,7 +544,7 @@ int hs_ba_drop_inactive_residuals(hs_ctx* c, int* n_dropped) {
   if (c->dirty) return fail(HS_ERR_STATE, "the window changed since hs_ba_fix_linearization");
   if (!c->tail_valid) return fail(HS_ERR_STATE, "hs_ba_fix_linearization must run first");
   // the tail's active flags through the context's pinned staging (a pageable copy is a synchronous staged one)
-  HS_HIP(c->rb_stage((size_t)std::max(c->nP, 1) * 8));
+  HS_TRY(c->rb_stage((size_t)std::max(c->nP, 1) * 8));
   const uint8_t* act = c->h_rb;
   if (c->nP > 0) {
     c->rb_pending = true;
@@ -709,7 +709,7 @@ int hs_ba_get_point_state(hs_ctx* c, float* idepth, float* idepth_zero, float* r
   const size_t n = c->nP;
   if (n == 0) return HS_OK;
   // through the context's pinned staging: asynchronous copies, one sync, then host copies
-  HS_HIP(c->rb_stage(5 * n * 4));
+  HS_TRY(c->rb_stage(5 * n * 4));
   void* dst[5] = {idepth, idepth_zero, relBL, nGood, HdiF};
   const void* src[5] = {c->d_idepth, c->d_idepth_zero, c->d_fix_relBL, c->d_fix_nGood, c->hdif_solved};
   c->rb_pending = true;

@@ -11,30 +11,9 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_extract.h"
 #include "hs_extract_kernels.h"
+#include "hs_host.h"
 #include "hs_sel_kernels.h"
 #include "hs_undist_kernels.h"
-
-namespace hs {
-extern thread_local std::string g_err;
-}
-
-namespace {
-int efail(int code, const std::string& msg) {
-  hs::g_err = msg;
-  return code;
-}
-}  // namespace
-
-#define EX_TRY(x)        \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-#define EX_HIP(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) return efail(HS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // one extract's outputs; two sets, so that an extract that overflows leaves the previous result untouched
 struct hs_extract_result {
@@ -43,12 +22,10 @@ struct hs_extract_result {
   uint8_t* blurred = nullptr;
 };
 
-struct hs_extractor {
-  int device = 0;
+struct hs_extractor : hs::Device {
+  hs::Pool pool;
   int W = 0, H = 0, cap = 0;
   int alloc = 0;  // min(cap, interior size): entries of the per-key arrays
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   hipEvent_t e_consumed = nullptr;  // a consumer's reads of the key arrays (hs_extract_keys_consumed)
   bool consumer_pending = false;
   int w[4] = {0, 0, 0, 0};
@@ -105,8 +82,8 @@ unsigned long long make_umax() {
 int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, const uint8_t* raw, int* n_keys) {
   hs_extract_result& r = e->res[e->cur ^ 1];
   hipStream_t s = e->stream;
-  EX_HIP(hipEventRecord(e->e0, s));
-  if (u) EX_HIP(hs_undist_enqueue(u, s, raw, nullptr, e->d_img));
+  HS_HIP(hipEventRecord(e->e0, s));
+  if (u) HS_HIP(hs_undist_enqueue(u, s, raw, nullptr, e->d_img));
   HsExtBlurArgs b;
   b.W = e->W;
   b.H = e->H;
@@ -115,7 +92,7 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
   b.dst = r.blurred;
   hipLaunchKernelGGL(hs_k_ext_blur, dim3((e->W + kExtBlurTileW - 1) / kExtBlurTileW, (e->H + kExtBlurTileH - 1) / kExtBlurTileH),
                      dim3(256), 0, s, b);
-  EX_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   HsExtKeysArgs k;
   k.W = e->W;
   k.H = e->H;
@@ -127,9 +104,9 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
   k.count = e->d_count;
   const int rows = e->H - 2 * kExtBorder;
   hipLaunchKernelGGL(hs_k_ext_count, dim3((rows + 3) / 4), dim3(256), 0, s, k);
-  EX_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   hipLaunchKernelGGL(hs_k_ext_write, dim3((rows + 3) / 4), dim3(256), 0, s, k);
-  EX_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   HsExtDescArgs d;
   d.W = e->W;
   d.cap = k.cap;
@@ -144,15 +121,15 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
   d.desc = r.desc;
   // a wave per key over a grid that does not depend on the count: the count is read on the device
   hipLaunchKernelGGL(hs_k_ext_desc, dim3(std::min((k.cap + 3) / 4, 2048)), dim3(256), 0, s, d);
-  EX_HIP(hipGetLastError());
-  EX_HIP(hipEventRecord(e->e1, s));
-  EX_HIP(hipMemcpyAsync(e->h_count, e->d_count, sizeof(int), hipMemcpyDeviceToHost, s));
-  EX_HIP(hipStreamSynchronize(s));  // the one wait of an extract
-  EX_HIP(hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipEventRecord(e->e1, s));
+  HS_HIP(hipMemcpyAsync(e->h_count, e->d_count, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));  // the one wait of an extract
+  HS_HIP(hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
   const int n = *e->h_count;
   if (n_keys) *n_keys = n;
   if (n > e->cap)
-    return efail(HS_ERR_INVALID, "extract yields " + std::to_string(n) + " keys, capacity is " + std::to_string(e->cap));
+    return hs::fail(HS_ERR_INVALID, "extract yields " + std::to_string(n) + " keys, capacity is " + std::to_string(e->cap));
   e->cur ^= 1;
   e->n = n;
   return HS_OK;
@@ -162,9 +139,9 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
 // writes the other set and only the one after it reuses the set being read, but ordering the very next extract
 // behind the consumer's reads costs nothing and needs no bookkeeping per set.
 int begin_extract(hs_extractor* e) {
-  EX_HIP(hipSetDevice(e->device));
+  HS_HIP(hipSetDevice(e->device));
   if (e->consumer_pending) {
-    EX_HIP(hipStreamWaitEvent(e->stream, e->e_consumed, 0));
+    HS_HIP(hipStreamWaitEvent(e->stream, e->e_consumed, 0));
     e->consumer_pending = false;
   }
   return HS_OK;
@@ -193,21 +170,18 @@ extern "C" {
 
 int hs_extractor_create(hs_extractor** out, int device_id, int width, int height, int capacity,
                         const int8_t pattern[1024]) {
-  if (!out) return efail(HS_ERR_INVALID, "null out");
+  if (!out) return hs::fail(HS_ERR_INVALID, "null out");
   *out = nullptr;
-  if (!pattern) return efail(HS_ERR_INVALID, "null pattern");
+  if (!pattern) return hs::fail(HS_ERR_INVALID, "null pattern");
   if (width < 2 * kExtBorder + 1 || height < 2 * kExtBorder + 1)
-    return efail(HS_ERR_INVALID, "image smaller than 39 x 39: no pixel lies 19 px from every edge");
-  if ((long long)width * height >= (1LL << 30)) return efail(HS_ERR_INVALID, "image too large");
-  if (capacity < 1) return efail(HS_ERR_INVALID, "capacity must be >= 1");
+    return hs::fail(HS_ERR_INVALID, "image smaller than 39 x 39: no pixel lies 19 px from every edge");
+  if ((long long)width * height >= (1LL << 30)) return hs::fail(HS_ERR_INVALID, "image too large");
+  if (capacity < 1) return hs::fail(HS_ERR_INVALID, "capacity must be >= 1");
   for (int i = 0; i < 1024; i++)
     if (pattern[i] < -kExtPatternMax || pattern[i] > kExtPatternMax)
-      return efail(HS_ERR_INVALID, "pattern entry " + std::to_string(i) + " outside +-13: a rotated tap could leave the image");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return efail(HS_ERR_HIP, "no HIP device");
-  if (device_id < 0 || device_id >= ndev) return efail(HS_ERR_INVALID, "bad device id");
+      return hs::fail(HS_ERR_INVALID, "pattern entry " + std::to_string(i) + " outside +-13: a rotated tap could leave the image");
+  HS_TRY(hs::check_device(device_id));
   hs_extractor* e = new hs_extractor();
-  e->device = device_id;
   e->W = width;
   e->H = height;
   e->cap = capacity;
@@ -217,37 +191,32 @@ int hs_extractor_create(hs_extractor** out, int device_id, int width, int height
   e->umax = make_umax();
   const size_t area = (size_t)width * height, c = e->alloc;
   int rc = [&]() -> int {
-    EX_HIP(hipSetDevice(device_id));
-    EX_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    EX_HIP(hipEventCreate(&e->e0));
-    EX_HIP(hipEventCreate(&e->e1));
-    EX_HIP(hipEventCreateWithFlags(&e->e_consumed, hipEventDisableTiming));
-    EX_HIP(hipMalloc((void**)&e->d_map, area * sizeof(float)));
-    EX_HIP(hipMalloc((void**)&e->d_img, area));
-    EX_HIP(hipMalloc((void**)&e->d_pattern, 1024));
-    EX_HIP(hipMalloc((void**)&e->d_row_cnt, (size_t)(height - 2 * kExtBorder) * sizeof(int)));
-    EX_HIP(hipMalloc((void**)&e->d_count, sizeof(int)));
-    EX_HIP(hipHostMalloc((void**)&e->h_count, sizeof(int), hipHostMallocDefault));
+    hs::Pool& m = e->pool;
+    HS_TRY(e->open(device_id));
+    HS_HIP(hipEventCreateWithFlags(&e->e_consumed, hipEventDisableTiming));
+    HS_TRY(m.alloc(&e->d_map, area));
+    HS_TRY(m.alloc(&e->d_img, area));
+    HS_TRY(m.alloc(&e->d_pattern, 256));
+    HS_TRY(m.alloc(&e->d_row_cnt, height - 2 * kExtBorder));
+    HS_TRY(m.alloc(&e->d_count, 1));
+    HS_TRY(m.pinned(&e->h_count, 1));
     for (hs_extract_result& r : e->res) {
-      EX_HIP(hipMalloc((void**)&r.x, c * sizeof(float)));
-      EX_HIP(hipMalloc((void**)&r.y, c * sizeof(float)));
-      EX_HIP(hipMalloc((void**)&r.angle, c * sizeof(float)));
-      EX_HIP(hipMalloc((void**)&r.desc, c * 32));
-      EX_HIP(hipMalloc((void**)&r.blurred, area));
+      HS_TRY(m.alloc(&r.x, c));
+      HS_TRY(m.alloc(&r.y, c));
+      HS_TRY(m.alloc(&r.angle, c));
+      HS_TRY(m.alloc(&r.desc, c * 8));
+      HS_TRY(m.alloc(&r.blurred, area));
       // fills on the kernels' own stream (hs_extractor_get before any extract reads blurred)
-      EX_HIP(hipMemsetAsync(r.blurred, 0, area, e->stream));
+      HS_HIP(hipMemsetAsync(r.blurred, 0, area, e->stream));
     }
-    EX_HIP(hipMemsetAsync(e->d_count, 0, sizeof(int), e->stream));
-    EX_HIP(hipMemcpyAsync(e->d_pattern, pattern, 1024, hipMemcpyHostToDevice, e->stream));
-    EX_HIP(hipStreamSynchronize(e->stream));  // pattern is the caller's
+    HS_HIP(hipMemsetAsync(e->d_count, 0, sizeof(int), e->stream));
+    HS_HIP(hipMemcpyAsync(e->d_pattern, pattern, 1024, hipMemcpyHostToDevice, e->stream));
+    HS_HIP(hipStreamSynchronize(e->stream));  // pattern is the caller's
     return HS_OK;
   }();
-  if (rc) {
-    hs_extractor_destroy(e);
-    return rc;
-  }
-  *out = e;
-  return HS_OK;
+  if (rc) hs_extractor_destroy(e);
+  else *out = e;
+  return rc;
 }
 
 void hs_extractor_destroy(hs_extractor* e) {
@@ -255,69 +224,59 @@ void hs_extractor_destroy(hs_extractor* e) {
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->consumer_pending) (void)hipEventSynchronize(e->e_consumed);  // a tracer may still be copying the keys
-  void* dev[] = {e->d_map, e->d_img, e->d_pattern, e->d_row_cnt, e->d_count};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  for (hs_extract_result& r : e->res) {
-    void* ps[] = {r.x, r.y, r.angle, r.desc, r.blurred};
-    for (void* p : ps)
-      if (p) (void)hipFree(p);
-  }
-  if (e->h_count) (void)hipHostFree(e->h_count);
-  if (e->e0) (void)hipEventDestroy(e->e0);
-  if (e->e1) (void)hipEventDestroy(e->e1);
+  e->pool.release_all();
   if (e->e_consumed) (void)hipEventDestroy(e->e_consumed);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  e->close();
   delete e;
 }
 
 int hs_extractor_extract(hs_extractor* e, const float* map, const uint8_t* img8, int* n_keys) {
-  if (!e || !map || !img8) return efail(HS_ERR_INVALID, "null argument");
-  EX_TRY(begin_extract(e));
+  if (!e || !map || !img8) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(begin_extract(e));
   const size_t area = (size_t)e->W * e->H;
-  EX_HIP(hipMemcpyAsync(e->d_map, map, area * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  EX_HIP(hipMemcpyAsync(e->d_img, img8, area, hipMemcpyHostToDevice, e->stream));
+  HS_HIP(hipMemcpyAsync(e->d_map, map, area * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  HS_HIP(hipMemcpyAsync(e->d_img, img8, area, hipMemcpyHostToDevice, e->stream));
   return run_extract(e, e->d_map, nullptr, nullptr, n_keys);
 }
 
 int hs_extractor_extract_selected(hs_extractor* e, hs_selector* s, const uint8_t* img8, int* n_keys) {
-  if (!e || !s || !img8) return efail(HS_ERR_INVALID, "null argument");
+  if (!e || !s || !img8) return hs::fail(HS_ERR_INVALID, "null argument");
   const float* d_map = nullptr;
   hipEvent_t ready = nullptr;
-  EX_TRY(hs_select_device_map(s, e->device, e->W, e->H, &d_map, &ready));
-  EX_TRY(begin_extract(e));
-  EX_HIP(hipStreamWaitEvent(e->stream, ready, 0));
-  EX_HIP(hipMemcpyAsync(e->d_img, img8, (size_t)e->W * e->H, hipMemcpyHostToDevice, e->stream));
+  HS_TRY(hs_select_device_map(s, e->device, e->W, e->H, &d_map, &ready));
+  HS_TRY(begin_extract(e));
+  HS_HIP(hipStreamWaitEvent(e->stream, ready, 0));
+  HS_HIP(hipMemcpyAsync(e->d_img, img8, (size_t)e->W * e->H, hipMemcpyHostToDevice, e->stream));
   return run_extract(e, d_map, nullptr, nullptr, n_keys);
 }
 
 int hs_extractor_extract_u8(hs_extractor* e, hs_selector* s, hs_undistorter* u, const uint8_t* raw, int* n_keys) {
-  if (!e || !s || !u || !raw) return efail(HS_ERR_INVALID, "null argument");
-  EX_TRY(hs_undist_match(u, e->device, e->W, e->H));
+  if (!e || !s || !u || !raw) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(hs_undist_match(u, e->device, e->W, e->H));
   const float* d_map = nullptr;
   hipEvent_t ready = nullptr;
-  EX_TRY(hs_select_device_map(s, e->device, e->W, e->H, &d_map, &ready));
-  EX_TRY(begin_extract(e));
-  EX_HIP(hipStreamWaitEvent(e->stream, ready, 0));
+  HS_TRY(hs_select_device_map(s, e->device, e->W, e->H, &d_map, &ready));
+  HS_TRY(begin_extract(e));
+  HS_HIP(hipStreamWaitEvent(e->stream, ready, 0));
   return run_extract(e, d_map, u, raw, n_keys);
 }
 
 int hs_extractor_get(hs_extractor* e, int* n, float* xy, float* angle, uint8_t* desc, uint8_t* blurred) {
-  if (!e) return efail(HS_ERR_INVALID, "null extractor");
-  EX_HIP(hipSetDevice(e->device));
+  if (!e) return hs::fail(HS_ERR_INVALID, "null extractor");
+  HS_HIP(hipSetDevice(e->device));
   const hs_extract_result& r = e->res[e->cur];
   const size_t m = e->n;
   if (n) *n = e->n;
   std::vector<float> hx(xy ? m : 0), hy(xy ? m : 0);
   hipStream_t s = e->stream;
   if (xy && m) {
-    EX_HIP(hipMemcpyAsync(hx.data(), r.x, m * sizeof(float), hipMemcpyDeviceToHost, s));
-    EX_HIP(hipMemcpyAsync(hy.data(), r.y, m * sizeof(float), hipMemcpyDeviceToHost, s));
+    HS_HIP(hipMemcpyAsync(hx.data(), r.x, m * sizeof(float), hipMemcpyDeviceToHost, s));
+    HS_HIP(hipMemcpyAsync(hy.data(), r.y, m * sizeof(float), hipMemcpyDeviceToHost, s));
   }
-  if (angle && m) EX_HIP(hipMemcpyAsync(angle, r.angle, m * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (desc && m) EX_HIP(hipMemcpyAsync(desc, r.desc, m * 32, hipMemcpyDeviceToHost, s));
-  if (blurred) EX_HIP(hipMemcpyAsync(blurred, r.blurred, (size_t)e->W * e->H, hipMemcpyDeviceToHost, s));
-  EX_HIP(hipStreamSynchronize(s));
+  if (angle && m) HS_HIP(hipMemcpyAsync(angle, r.angle, m * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (desc && m) HS_HIP(hipMemcpyAsync(desc, r.desc, m * 32, hipMemcpyDeviceToHost, s));
+  if (blurred) HS_HIP(hipMemcpyAsync(blurred, r.blurred, (size_t)e->W * e->H, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   for (size_t i = 0; i < hx.size(); i++) {
     xy[2 * i] = hx[i];
     xy[2 * i + 1] = hy[i];
@@ -326,7 +285,7 @@ int hs_extractor_get(hs_extractor* e, int* n, float* xy, float* angle, uint8_t* 
 }
 
 int hs_extractor_last_stats(hs_extractor* e, double* ms) {
-  if (!e) return efail(HS_ERR_INVALID, "null extractor");
+  if (!e) return hs::fail(HS_ERR_INVALID, "null extractor");
   if (ms) *ms = e->last_ms;
   return HS_OK;
 }

@@ -12,18 +12,10 @@
 #include <vector>
 
 #include "../../include/hs_refine.h"
+#include "hs_host.h"
 #include "hs_refine_kernels.h"
 
-namespace hs {
-extern thread_local std::string g_err;
-}
-
 namespace {
-int rfail(int code, const std::string& msg) {
-  hs::g_err = msg;
-  return code;
-}
-
 // Eigen compute_inverse_size3 in double (CalibData: pyrKi[0] = pyrK[0].inverse(), Include/CalibData.h:150)
 void inv3d(const double m[9], double r[9]) {
   auto M = [&](int i, int j) { return m[i * 3 + j]; };
@@ -39,25 +31,12 @@ void inv3d(const double m[9], double r[9]) {
 }
 }  // namespace
 
-#define RF_HIP(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) return rfail(HS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define RF_TRY(x)        \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-
 // per-point planes of the device state block (floats unless noted)
 enum { PF_U, PF_V, PF_INVZ, PF_ID, PF_IDN, PF_IR, PF_E0, PF_E1, PF_EN0, PF_EN1, PF_LH, PF_LHN, PF_MS, PF_JB0 = PF_MS + 1,
        PF_COUNT = PF_JB0 + 20 };
 
-struct hs_refiner {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+struct hs_refiner : hs::Device {
+  hs::Pool pool;
   int W = 0, H = 0;
   double K4[4] = {0, 0, 0, 0};
   double Ki[9];
@@ -119,16 +98,16 @@ static HsRefArgs make_args(hs_refiner* r, int mode) {
 
 static int enqueue(hs_refiner* r, const HsRefArgs& a) {
   hipLaunchKernelGGL(hs_k_refine_step, dim3(a.nblocks), dim3(256), 0, r->stream, a);
-  RF_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   return HS_OK;
 }
 
 static int dump_trace(hs_refiner* r, int nb, int launch_no) {
   std::vector<long long> t((size_t)nb * 16);
-  RF_HIP(hipMemcpyAsync(t.data(), r->d_trace, t.size() * sizeof(long long), hipMemcpyDeviceToHost, r->stream));
-  RF_HIP(hipStreamSynchronize(r->stream));
+  HS_HIP(hipMemcpyAsync(t.data(), r->d_trace, t.size() * sizeof(long long), hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipStreamSynchronize(r->stream));
   int khz = 0;
-  RF_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, r->device));
+  HS_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, r->device));
   const double us = khz > 0 ? 1e3 / khz : 0.01;
   long long t0 = t[0];
   for (int b = 0; b < nb; b++) t0 = std::min(t0, t[(size_t)b * 16]);
@@ -143,66 +122,66 @@ static int dump_trace(hs_refiner* r, int nb, int launch_no) {
     std::fprintf(stderr, "[hs refine trace] launch %d cp%d n %3zu min %7.2f med %7.2f max %7.2f us\n", launch_no, k,
                  v.size(), v.front(), v[v.size() / 2], v.back());
   }
-  RF_HIP(hipMemsetAsync(r->d_trace, 0, t.size() * sizeof(long long), r->stream));
+  HS_HIP(hipMemsetAsync(r->d_trace, 0, t.size() * sizeof(long long), r->stream));
   return HS_OK;
 }
 
 static int read_ctl(hs_refiner* r) {
-  RF_HIP(hipMemcpyAsync(r->h_ctl, r->d_ctl, sizeof(HsRefCtl), hipMemcpyDeviceToHost, r->stream));
-  RF_HIP(hipStreamSynchronize(r->stream));
+  HS_HIP(hipMemcpyAsync(r->h_ctl, r->d_ctl, sizeof(HsRefCtl), hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipStreamSynchronize(r->stream));
   return HS_OK;
 }
 
 static int check_ready(hs_refiner* r) {
-  if (!r->haveFrames) return rfail(HS_ERR_STATE, "hs_refiner_set_frames first");
-  if (r->n <= 0) return rfail(HS_ERR_STATE, "hs_refiner_set_points first");
-  RF_HIP(hipSetDevice(r->device));
+  if (!r->haveFrames) return hs::fail(HS_ERR_STATE, "hs_refiner_set_frames first");
+  if (r->n <= 0) return hs::fail(HS_ERR_STATE, "hs_refiner_set_points first");
+  HS_HIP(hipSetDevice(r->device));
   return HS_OK;
 }
 
 // resetPoints + one calcResAndGS at (T, aff)
 static int run_calc(hs_refiner* r, const double T7[7], const double aff[2]) {
-  RF_TRY(check_ready(r));
+  HS_TRY(check_ready(r));
   HsRefArgs a = make_args(r, HS_REF_CALC);
   hs_ref_pass_consts(T7, aff, r->Ki, r->n, &a.pc0);
-  RF_HIP(hipEventRecord(r->e0, r->stream));
-  RF_TRY(enqueue(r, a));
-  RF_HIP(hipEventRecord(r->e1, r->stream));
-  RF_TRY(read_ctl(r));
+  HS_HIP(hipEventRecord(r->e0, r->stream));
+  HS_TRY(enqueue(r, a));
+  HS_HIP(hipEventRecord(r->e1, r->stream));
+  HS_TRY(read_ctl(r));
   float ms = 0;
-  RF_HIP(hipEventElapsedTime(&ms, r->e0, r->e1));
+  HS_HIP(hipEventElapsedTime(&ms, r->e0, r->e1));
   r->last_ms = ms;
   return HS_OK;
 }
 
 // Refine: the first pass, then LM steps enqueued in batches until the device sets done, then the final applyStep
 static int run_refine(hs_refiner* r, const double T7[7], const double aff[2]) {
-  RF_TRY(check_ready(r));
+  HS_TRY(check_ready(r));
   HsRefArgs a = make_args(r, HS_REF_INIT);
   hs_ref_pass_consts(T7, aff, r->Ki, r->n, &a.pc0);
   for (int q = 0; q < 7; q++) a.T0[q] = T7[q];
   a.aff0[0] = aff[0];
   a.aff0[1] = aff[1];
-  RF_HIP(hipEventRecord(r->e0, r->stream));
-  RF_TRY(enqueue(r, a));
+  HS_HIP(hipEventRecord(r->e0, r->stream));
+  HS_TRY(enqueue(r, a));
   HsRefArgs it = make_args(r, HS_REF_ITER);
   int launched = 0, batch = 4;
   if (r->d_trace) batch = 1;
   for (;;) {
-    for (int k = 0; k < batch; k++) RF_TRY(enqueue(r, it));
-    if (r->d_trace && launched < 3) RF_TRY(dump_trace(r, it.nblocks, launched));
+    for (int k = 0; k < batch; k++) HS_TRY(enqueue(r, it));
+    if (r->d_trace && launched < 3) HS_TRY(dump_trace(r, it.nblocks, launched));
     launched += batch;
-    RF_HIP(hipMemcpyAsync(&r->h_flags[0], &r->d_ctl->done, sizeof(int), hipMemcpyDeviceToHost, r->stream));
-    RF_HIP(hipStreamSynchronize(r->stream));
+    HS_HIP(hipMemcpyAsync(&r->h_flags[0], &r->d_ctl->done, sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    HS_HIP(hipStreamSynchronize(r->stream));
     if (r->h_flags[0]) break;
-    if (launched > HS_REF_MAXLOG + 8) return rfail(HS_ERR_STATE, "refine did not stop within the iteration cap");
+    if (launched > HS_REF_MAXLOG + 8) return hs::fail(HS_ERR_STATE, "refine did not stop within the iteration cap");
     if (!r->d_trace) batch = std::min(2 * batch, 32);
   }
-  RF_TRY(enqueue(r, make_args(r, HS_REF_FINAL)));  // the pending applyStep + optReg of the last accepted pass
-  RF_HIP(hipEventRecord(r->e1, r->stream));
-  RF_TRY(read_ctl(r));
+  HS_TRY(enqueue(r, make_args(r, HS_REF_FINAL)));  // the pending applyStep + optReg of the last accepted pass
+  HS_HIP(hipEventRecord(r->e1, r->stream));
+  HS_TRY(read_ctl(r));
   float ms = 0;
-  RF_HIP(hipEventElapsedTime(&ms, r->e0, r->e1));
+  HS_HIP(hipEventElapsedTime(&ms, r->e0, r->e1));
   r->last_ms = ms;
   r->jb_sel = r->h_ctl->jb_sel ^ r->h_ctl->apply_prev;
   r->last_iters = r->h_ctl->iteration + 1;
@@ -212,62 +191,47 @@ static int run_refine(hs_refiner* r, const double T7[7], const double aff[2]) {
 extern "C" {
 
 int hs_refiner_create(hs_refiner** out, int device_id, int width, int height, const double K4[4]) {
-  if (!out || !K4 || width < 8 || height < 8) return rfail(HS_ERR_INVALID, "bad refiner arguments");
+  if (!out || !K4 || width < 8 || height < 8) return hs::fail(HS_ERR_INVALID, "bad refiner arguments");
+  *out = nullptr;
+  HS_TRY(hs::check_device(device_id));
   hs_refiner* r = new hs_refiner();
-  r->device = device_id;
   r->W = width;
   r->H = height;
   for (int q = 0; q < 4; q++) r->K4[q] = K4[q];
   const double K[9] = {K4[0], 0, K4[2], 0, K4[1], K4[3], 0, 0, 1};
   inv3d(K, r->Ki);
   const size_t np = (size_t)width * height;
-  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&r->e0) != hipSuccess || hipEventCreate(&r->e1) != hipSuccess ||
-      hipMalloc(&r->d_img1, np * sizeof(float4)) != hipSuccess || hipMalloc(&r->d_img2, np * sizeof(float4)) != hipSuccess ||
-      hipMalloc(&r->d_ctl, sizeof(HsRefCtl)) != hipSuccess || hipHostMalloc(&r->h_ctl, sizeof(HsRefCtl)) != hipSuccess ||
-      hipHostMalloc(&r->h_flags, 4 * sizeof(int)) != hipSuccess || hipMalloc(&r->d_ticket, sizeof(int)) != hipSuccess ||
-      hipMemsetAsync(r->d_ticket, 0, sizeof(int), r->stream) != hipSuccess ||
-      hipMemsetAsync(r->d_ctl, 0, sizeof(HsRefCtl), r->stream) != hipSuccess ||
-      hipMalloc(&r->d_log, sizeof(float) * HS_REF_MAXLOG * HS_REF_LOGW) != hipSuccess) {
-    hs_refiner_destroy(r);
-    return rfail(HS_ERR_HIP, "refiner allocation failed");
-  }
-  *out = r;
-  return HS_OK;
+  hs::Pool& m = r->pool;
+  int rc = HS_OK;
+  if (r->open(device_id) || m.alloc(&r->d_img1, np) || m.alloc(&r->d_img2, np) || m.pinned(&r->h_ctl, 1) ||
+      m.pinned(&r->h_flags, 4) || m.alloc_zero(&r->d_ticket, 1, r->stream) || m.alloc_zero(&r->d_ctl, 1, r->stream) ||
+      m.alloc(&r->d_log, (size_t)HS_REF_MAXLOG * HS_REF_LOGW))
+    rc = hs::fail(HS_ERR_HIP, "refiner allocation failed");
+  if (rc) hs_refiner_destroy(r);
+  else *out = r;
+  return rc;
 }
 
 void hs_refiner_destroy(hs_refiner* r) {
   if (!r) return;
   (void)hipSetDevice(r->device);
   if (r->stream) (void)hipStreamSynchronize(r->stream);
-  (void)hipFree(r->d_img1);
-  (void)hipFree(r->d_img2);
-  (void)hipFree(r->d_pf);
-  (void)hipFree(r->d_pb);
-  (void)hipFree(r->d_ctl);
-  (void)hipFree(r->d_part);
-  (void)hipFree(r->d_ticket);
-  (void)hipFree(r->d_trace);
-  (void)hipFree(r->d_log);
-  if (r->h_ctl) (void)hipHostFree(r->h_ctl);
-  if (r->h_flags) (void)hipHostFree(r->h_flags);
-  if (r->e0) (void)hipEventDestroy(r->e0);
-  if (r->e1) (void)hipEventDestroy(r->e1);
-  if (r->stream) (void)hipStreamDestroy(r->stream);
+  r->pool.release_all();
+  r->close();
   delete r;
 }
 
 int hs_refiner_set_frames(hs_refiner* r, const float* first, const float* second, float e1, float e2) {
-  if (!r || !first || !second) return rfail(HS_ERR_INVALID, "null frame");
-  RF_HIP(hipSetDevice(r->device));
+  if (!r || !first || !second) return hs::fail(HS_ERR_INVALID, "null frame");
+  HS_HIP(hipSetDevice(r->device));
   const size_t np = (size_t)r->W * r->H;
   std::vector<float4> tex(np);
   float4* dst[2] = {r->d_img1, r->d_img2};
   const float* src[2] = {first, second};
   for (int f = 0; f < 2; f++) {
-    for (size_t i = 0; i < np; i++) tex[i] = make_float4(src[f][3 * i], src[f][3 * i + 1], src[f][3 * i + 2], 0.f);
-    RF_HIP(hipMemcpyAsync(dst[f], tex.data(), np * sizeof(float4), hipMemcpyHostToDevice, r->stream));
-    RF_HIP(hipStreamSynchronize(r->stream));  // tex is reused
+    hs::texels_from_triplets(tex.data(), src[f], np);
+    HS_HIP(hipMemcpyAsync(dst[f], tex.data(), np * sizeof(float4), hipMemcpyHostToDevice, r->stream));
+    HS_HIP(hipStreamSynchronize(r->stream));  // tex is reused
   }
   r->expo1 = e1;
   r->expo2 = e2;
@@ -276,29 +240,23 @@ int hs_refiner_set_frames(hs_refiner* r, const float* first, const float* second
 }
 
 int hs_refiner_set_points(hs_refiner* r, int n, const float* u, const float* v, const uint8_t* tri, const float* z) {
-  if (!r || n <= 0 || !u || !v || !tri || !z) return rfail(HS_ERR_INVALID, "bad points");
+  if (!r || n <= 0 || !u || !v || !tri || !z) return hs::fail(HS_ERR_INVALID, "bad points");
   for (int i = 0; i < n; i++)
     if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || u[i] < 0 || v[i] < 0 || u[i] > r->W - 1 || v[i] > r->H - 1)
-      return rfail(HS_ERR_INVALID, "keypoint outside the image");
-  RF_HIP(hipSetDevice(r->device));
-  (void)hipFree(r->d_pf);
-  (void)hipFree(r->d_pb);
-  (void)hipFree(r->d_part);
-  r->d_pf = nullptr;
-  r->d_pb = nullptr;
-  r->d_part = nullptr;
+      return hs::fail(HS_ERR_INVALID, "keypoint outside the image");
+  HS_HIP(hipSetDevice(r->device));
+  hs::Pool& m = r->pool;
+  m.release(&r->d_pf);
+  m.release(&r->d_pb);
+  m.release(&r->d_part);
+  m.release(&r->d_trace);
   r->n = 0;
   r->cap = n;  // planes of exactly n: the [2][n] energy blocks are two adjacent planes
-  RF_HIP(hipMalloc(&r->d_pf, sizeof(float) * PF_COUNT * (size_t)n));
-  RF_HIP(hipMalloc(&r->d_pb, 3 * (size_t)n));
-  RF_HIP(hipMalloc(&r->d_part, sizeof(double) * HS_REF_NRED * (size_t)((n + HS_REF_PPB - 1) / HS_REF_PPB)));
-  (void)hipFree(r->d_trace);
-  r->d_trace = nullptr;
-  if (const char* e = std::getenv("HS_REF_TRACE"); e && std::atoi(e) > 0) {
-    RF_HIP(hipMalloc(&r->d_trace, sizeof(long long) * 16 * (size_t)((n + HS_REF_PPB - 1) / HS_REF_PPB)));
-    RF_HIP(hipMemsetAsync(r->d_trace, 0, sizeof(long long) * 16 * (size_t)((n + HS_REF_PPB - 1) / HS_REF_PPB),
-                          r->stream));
-  }
+  const size_t nb = (size_t)((n + HS_REF_PPB - 1) / HS_REF_PPB);
+  HS_TRY(m.alloc(&r->d_pf, PF_COUNT * (size_t)n));
+  HS_TRY(m.alloc(&r->d_pb, 3 * (size_t)n));
+  HS_TRY(m.alloc(&r->d_part, HS_REF_NRED * nb));
+  if (const char* e = std::getenv("HS_REF_TRACE"); e && std::atoi(e) > 0) HS_TRY(m.alloc_zero(&r->d_trace, 16 * nb, r->stream));
   // the ctor's Pnt set-up (Src/Initializer.cpp:1362-1382)
   std::vector<float> pf((size_t)PF_COUNT * n, 0.f);
   std::vector<uint8_t> pb(3 * (size_t)n, 0);
@@ -313,9 +271,9 @@ int hs_refiner_set_points(hs_refiner* r, int n, const float* u, const float* v, 
     pb[i] = tri[i] ? 1 : 0;
     pb[n + i] = 1;  // isGood
   }
-  RF_HIP(hipMemcpyAsync(r->d_pf, pf.data(), pf.size() * sizeof(float), hipMemcpyHostToDevice, r->stream));
-  RF_HIP(hipMemcpyAsync(r->d_pb, pb.data(), pb.size(), hipMemcpyHostToDevice, r->stream));
-  RF_HIP(hipStreamSynchronize(r->stream));
+  HS_HIP(hipMemcpyAsync(r->d_pf, pf.data(), pf.size() * sizeof(float), hipMemcpyHostToDevice, r->stream));
+  HS_HIP(hipMemcpyAsync(r->d_pb, pb.data(), pb.size(), hipMemcpyHostToDevice, r->stream));
+  HS_HIP(hipStreamSynchronize(r->stream));
   r->n = n;
   r->jb_sel = 0;
   r->last_iters = 0;
@@ -324,10 +282,10 @@ int hs_refiner_set_points(hs_refiner* r, int n, const float* u, const float* v, 
 
 int hs_refiner_refine(hs_refiner* r, double pose[7], float* idepth_out, uint8_t* good_out, int* iterations,
                       int* snapped) {
-  if (!r || !pose) return rfail(HS_ERR_INVALID, "null");
+  if (!r || !pose) return hs::fail(HS_ERR_INVALID, "null");
   double aff[2] = {0, 0};  // thisToNext_aff = AffLight(0, 0)
   if (r->expo1 > 0 && r->expo2 > 0) aff[0] = (double)logf(r->expo2 / r->expo1);
-  RF_TRY(run_refine(r, pose, aff));
+  HS_TRY(run_refine(r, pose, aff));
   const HsRefCtl& o = *r->h_ctl;
   for (int q = 0; q < 7; q++) pose[q] = o.T[q];
   if (iterations) *iterations = r->last_iters;
@@ -337,23 +295,23 @@ int hs_refiner_refine(hs_refiner* r, double pose[7], float* idepth_out, uint8_t*
     std::vector<float> id(n);
     std::vector<uint8_t> tri(n), good(n);
     const HsRefPoints p = points_of(r);
-    RF_HIP(hipMemcpyAsync(id.data(), p.idepth, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-    RF_HIP(hipMemcpyAsync(tri.data(), p.tri, n, hipMemcpyDeviceToHost, r->stream));
-    RF_HIP(hipMemcpyAsync(good.data(), p.good, n, hipMemcpyDeviceToHost, r->stream));
-    RF_HIP(hipStreamSynchronize(r->stream));
+    HS_HIP(hipMemcpyAsync(id.data(), p.idepth, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    HS_HIP(hipMemcpyAsync(tri.data(), p.tri, n, hipMemcpyDeviceToHost, r->stream));
+    HS_HIP(hipMemcpyAsync(good.data(), p.good, n, hipMemcpyDeviceToHost, r->stream));
+    HS_HIP(hipStreamSynchronize(r->stream));
     for (size_t i = 0; i < n; i++) {
       if (good_out) good_out[i] = good[i];
       if (idepth_out && good[i] && tri[i]) idepth_out[i] = id[i];  // _videpth write-back (:1389-1395)
     }
   }
-  if (!std::isfinite(o.resOld[0])) return rfail(HS_ERR_NONFINITE, "non-finite refinement energy");
+  if (!std::isfinite(o.resOld[0])) return hs::fail(HS_ERR_NONFINITE, "non-finite refinement energy");
   return HS_OK;
 }
 
 int hs_refiner_calc_res(hs_refiner* r, const double T7[7], const double aff[2], float* H64, float* b8, float* Hsc64,
                         float* bsc8, float res3[3]) {
-  if (!r || !T7 || !aff) return rfail(HS_ERR_INVALID, "null");
-  RF_TRY(run_calc(r, T7, aff));
+  if (!r || !T7 || !aff) return hs::fail(HS_ERR_INVALID, "null");
+  HS_TRY(run_calc(r, T7, aff));
   const HsRefCtl& o = *r->h_ctl;
   if (H64) std::memcpy(H64, o.H, sizeof(o.H));
   if (b8) std::memcpy(b8, o.b, sizeof(o.b));
@@ -364,15 +322,15 @@ int hs_refiner_calc_res(hs_refiner* r, const double T7[7], const double aff[2], 
 }
 
 int hs_refiner_get_points(hs_refiner* r, float* f7, uint8_t* g2, float* jb_new) {
-  if (!r || !f7 || !g2) return rfail(HS_ERR_INVALID, "null");
-  if (r->n <= 0) return rfail(HS_ERR_STATE, "no points");
-  RF_HIP(hipSetDevice(r->device));
+  if (!r || !f7 || !g2) return hs::fail(HS_ERR_INVALID, "null");
+  if (r->n <= 0) return hs::fail(HS_ERR_STATE, "no points");
+  HS_HIP(hipSetDevice(r->device));
   const size_t n = r->n;
   std::vector<float> pf((size_t)PF_COUNT * n);
   std::vector<uint8_t> pb(3 * n);
-  RF_HIP(hipMemcpyAsync(pf.data(), r->d_pf, pf.size() * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-  RF_HIP(hipMemcpyAsync(pb.data(), r->d_pb, pb.size(), hipMemcpyDeviceToHost, r->stream));
-  RF_HIP(hipStreamSynchronize(r->stream));
+  HS_HIP(hipMemcpyAsync(pf.data(), r->d_pf, pf.size() * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipMemcpyAsync(pb.data(), r->d_pb, pb.size(), hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipStreamSynchronize(r->stream));
   const int planes[7] = {PF_ID, PF_IDN, PF_IR, PF_EN0, PF_EN1, PF_MS, PF_LHN};
   for (size_t i = 0; i < n; i++) {
     for (int k = 0; k < 7; k++) f7[7 * i + k] = pf[planes[k] * n + i];
@@ -388,19 +346,19 @@ int hs_refiner_get_points(hs_refiner* r, float* f7, uint8_t* g2, float* jb_new) 
 }
 
 int hs_refiner_get_log(hs_refiner* r, int cap, float* out) {
-  if (!r || (cap > 0 && !out)) return rfail(HS_ERR_INVALID, "null");
+  if (!r || (cap > 0 && !out)) return hs::fail(HS_ERR_INVALID, "null");
   const int n = std::min(r->last_iters, HS_REF_MAXLOG);
   const int m = std::min(n, cap);
   if (m > 0) {
-    RF_HIP(hipSetDevice(r->device));
-    RF_HIP(hipStreamSynchronize(r->stream));
-    RF_HIP(hipMemcpy(out, r->d_log, sizeof(float) * HS_REF_LOGW * m, hipMemcpyDeviceToHost));
+    HS_HIP(hipSetDevice(r->device));
+    HS_HIP(hipStreamSynchronize(r->stream));
+    HS_HIP(hipMemcpy(out, r->d_log, sizeof(float) * HS_REF_LOGW * m, hipMemcpyDeviceToHost));
   }
   return n;
 }
 
 int hs_refiner_last_ms(hs_refiner* r, double* ms) {
-  if (!r || !ms) return rfail(HS_ERR_INVALID, "null");
+  if (!r || !ms) return hs::fail(HS_ERR_INVALID, "null");
   *ms = r->last_ms;
   return HS_OK;
 }

@@ -11,36 +11,13 @@
 
 #include "../../include/hs_ba.h"
 #include "../../include/hs_select.h"
+#include "hs_host.h"
 #include "hs_pyr_kernels.h"
 #include "hs_sel_kernels.h"
 
-namespace hs {
-extern thread_local std::string g_err;
-}
-
-namespace {
-int sfail(int code, const std::string& msg) {
-  hs::g_err = msg;
-  return code;
-}
-}  // namespace
-
-#define SL_TRY(x)        \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-#define SL_HIP(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) return sfail(HS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-struct hs_selector {
+struct hs_selector : hs::Device {
   hs_params P;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hs::Pool pool;
   int W = 0, H = 0, w1 = 0, w2 = 0, w32 = 0, h32 = 0;
   int currentPotential = 3;
   int gradHistFrame = -1;
@@ -69,17 +46,14 @@ struct hs_selector {
 static int n4(int n, int pot) { return (n + 4 * pot - 1) / (4 * pot); }
 
 extern "C" int hs_selector_create(hs_selector** out, const hs_params* params, int device_id, int width, int height) {
-  if (!out) return sfail(HS_ERR_INVALID, "null out");
+  if (!out) return hs::fail(HS_ERR_INVALID, "null out");
   *out = nullptr;
-  if (width < 32 || height < 32) return sfail(HS_ERR_INVALID, "image smaller than one 32x32 histogram cell");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(HS_ERR_HIP, "no HIP device");
-  if (device_id < 0 || device_id >= ndev) return sfail(HS_ERR_INVALID, "bad device id");
+  if (width < 32 || height < 32) return hs::fail(HS_ERR_INVALID, "image smaller than one 32x32 histogram cell");
+  HS_TRY(hs::check_device(device_id));
   hs_selector* s = new hs_selector();
   *out = s;
   if (params) s->P = *params;
   else hs_params_default(&s->P);
-  s->device = device_id;
   s->W = width;
   s->H = height;
   s->w1 = width >> 1;
@@ -97,33 +71,31 @@ extern "C" int hs_selector_create(hs_selector** out, const hs_params* params, in
   std::srand(3141592);
   for (size_t i = 0; i < area; ++i) pat[i] = rand() & 0xFF;
   int rc = [&]() -> int {
-    SL_HIP(hipSetDevice(device_id));
-    SL_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    SL_HIP(hipEventCreate(&s->e0));
-    SL_HIP(hipEventCreate(&s->e1));
-    SL_HIP(hipMalloc((void**)&s->d_pattern, area));
-    SL_HIP(hipMalloc((void**)&s->d_ths, s->nths * sizeof(float)));
-    SL_HIP(hipMalloc((void**)&s->d_thsS, s->nths * sizeof(float)));
-    SL_HIP(hipMalloc((void**)&s->d_ticket, sizeof(unsigned int)));
-    SL_HIP(hipMalloc((void**)&s->d_dI, area * 3 * sizeof(float)));
+    hs::Pool& m = s->pool;
+    HS_TRY(s->open(device_id));
+    HS_TRY(m.alloc(&s->d_pattern, area));
+    HS_TRY(m.alloc(&s->d_ths, s->nths));
+    HS_TRY(m.alloc(&s->d_thsS, s->nths));
+    HS_TRY(m.alloc(&s->d_ticket, 1));
+    HS_TRY(m.alloc(&s->d_dI, area * 3));
     for (int l = 0; l < 3; l++) {
       const size_t n = (size_t)(width >> l) * (height >> l);
-      SL_HIP(hipMalloc((void**)&s->d_lvl[l], n * sizeof(float4)));
-      SL_HIP(hipMalloc((void**)&s->d_g[l], n * sizeof(float)));
+      HS_TRY(m.alloc(&s->d_lvl[l], n));
+      HS_TRY(m.alloc(&s->d_g[l], n));
     }
-    SL_HIP(hipMalloc((void**)&s->d_raw, area * sizeof(float)));
-    SL_HIP(hipMalloc((void**)&s->d_map, area * sizeof(float)));
-    SL_HIP(hipMalloc((void**)&s->d_mask, (size_t)s->max_slots * sizeof(uint16_t)));
-    SL_HIP(hipMalloc((void**)&s->d_n2b, (size_t)s->max_slots * sizeof(int)));
-    SL_HIP(hipMalloc((void**)&s->d_has2, (size_t)s->max_slots));
-    SL_HIP(hipMalloc((void**)&s->d_counts, 4 * sizeof(int)));
-    SL_HIP(hipHostMalloc((void**)&s->h_counts, 4 * sizeof(int), hipHostMallocDefault));
-    SL_HIP(hipMalloc((void**)&s->d_tiles, (size_t)s->max_tiles * sizeof(int)));
-    SL_HIP(hipMemcpyAsync(s->d_pattern, pat.data(), area, hipMemcpyHostToDevice, s->stream));
-    SL_HIP(hipMemsetAsync(s->d_ths, 0, s->nths * sizeof(float), s->stream));
-    SL_HIP(hipMemsetAsync(s->d_thsS, 0, s->nths * sizeof(float), s->stream));
-    SL_HIP(hipMemsetAsync(s->d_ticket, 0, sizeof(unsigned int), s->stream));
-    SL_HIP(hipStreamSynchronize(s->stream));
+    HS_TRY(m.alloc(&s->d_raw, area));
+    HS_TRY(m.alloc(&s->d_map, area));
+    HS_TRY(m.alloc(&s->d_mask, s->max_slots));
+    HS_TRY(m.alloc(&s->d_n2b, s->max_slots));
+    HS_TRY(m.alloc(&s->d_has2, s->max_slots));
+    HS_TRY(m.alloc(&s->d_counts, 4));
+    HS_TRY(m.pinned(&s->h_counts, 4));
+    HS_TRY(m.alloc(&s->d_tiles, s->max_tiles));
+    HS_HIP(hipMemcpyAsync(s->d_pattern, pat.data(), area, hipMemcpyHostToDevice, s->stream));
+    HS_HIP(hipMemsetAsync(s->d_ths, 0, s->nths * sizeof(float), s->stream));
+    HS_HIP(hipMemsetAsync(s->d_thsS, 0, s->nths * sizeof(float), s->stream));
+    HS_HIP(hipMemsetAsync(s->d_ticket, 0, sizeof(unsigned int), s->stream));
+    HS_HIP(hipStreamSynchronize(s->stream));
     return HS_OK;
   }();
   if (rc) {
@@ -137,15 +109,8 @@ extern "C" void hs_selector_destroy(hs_selector* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
-  void* dev[] = {s->d_pattern, s->d_ths, s->d_thsS, s->d_ticket, s->d_dI, s->d_lvl[0], s->d_lvl[1], s->d_lvl[2],
-                 s->d_g[0], s->d_g[1], s->d_g[2], s->d_raw, s->d_map, s->d_mask, s->d_n2b, s->d_has2, s->d_counts,
-                 s->d_tiles};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (s->h_counts) (void)hipHostFree(s->h_counts);
-  if (s->e0) (void)hipEventDestroy(s->e0);
-  if (s->e1) (void)hipEventDestroy(s->e1);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
+  s->pool.release_all();
+  s->close();
   delete s;
 }
 
@@ -160,7 +125,7 @@ int run_select(hs_selector* s, const float* dI, int dstride, int pot, float thFa
   a.n4x = n4(s->W, pot);
   a.n4y = n4(s->H, pot);
   a.nslots = a.n4x * a.n4y * 16;
-  if (a.nslots > s->max_slots) return sfail(HS_ERR_INVALID, "slot table overflow");
+  if (a.nslots > s->max_slots) return hs::fail(HS_ERR_INVALID, "slot table overflow");
   a.dI = dI;
   a.dstride = dstride;
   a.g0 = s->d_g[0];
@@ -180,16 +145,16 @@ int run_select(hs_selector* s, const float* dI, int dstride, int pot, float thFa
   a.has2 = s->d_has2;
   a.map = s->d_map;
   a.counts = s->d_counts;
-  SL_HIP(hipMemsetAsync(s->d_map, 0, (size_t)s->W * s->H * sizeof(float), s->stream));
-  SL_HIP(hipMemsetAsync(s->d_counts, 0, 4 * sizeof(int), s->stream));
+  HS_HIP(hipMemsetAsync(s->d_map, 0, (size_t)s->W * s->H * sizeof(float), s->stream));
+  HS_HIP(hipMemsetAsync(s->d_counts, 0, 4 * sizeof(int), s->stream));
   hipLaunchKernelGGL(hs_k_sel_mask, dim3((a.nslots * 16 + 255) / 256), dim3(256), 0, s->stream, a);  // 16 lanes / slot
-  SL_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   hipLaunchKernelGGL(hs_k_sel_scan, dim3(1), dim3(1024), 0, s->stream, a);
-  SL_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   hipLaunchKernelGGL(hs_k_sel_pick, dim3((a.nslots * 4 + 255) / 256), dim3(256), 0, s->stream, a);  // 4 lanes / slot
-  SL_HIP(hipGetLastError());
-  SL_HIP(hipMemcpyAsync(s->h_counts, s->d_counts, 4 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  SL_HIP(hipStreamSynchronize(s->stream));
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(s->h_counts, s->d_counts, 4 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HS_HIP(hipStreamSynchronize(s->stream));
   s->last_passes++;
   return HS_OK;
 }
@@ -207,7 +172,7 @@ int run_hists(hs_selector* s) {
   h.thsSmoothed = s->d_thsS;
   h.ticket = s->d_ticket;
   hipLaunchKernelGGL(hs_k_sel_hist, dim3(s->w32 * s->h32), dim3(256), 0, s->stream, h);
-  SL_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   return HS_OK;
 }
 
@@ -219,11 +184,11 @@ int make_maps(hs_selector* s, const float* dI, int dstride, int id, float densit
   float quotia;
   int idealPotential = s->currentPotential;
   if (id != s->gradHistFrame || !s->hists_valid) {
-    SL_TRY(run_hists(s));
+    HS_TRY(run_hists(s));
     s->gradHistFrame = id;
     s->hists_valid = true;
   }
-  SL_TRY(run_select(s, dI, dstride, s->currentPotential, thFactor));
+  HS_TRY(run_select(s, dI, dstride, s->currentPotential, thFactor));
   numHave = s->h_counts[0] + s->h_counts[1] + s->h_counts[2];
   quotia = numWant / numHave;
   const float K = numHave * (s->currentPotential + 1) * (s->currentPotential + 1);
@@ -249,13 +214,13 @@ int make_maps(hs_selector* s, const float* dI, int dstride, int id, float densit
     b.charTH = (unsigned char)(255 * quotia);
     b.removed = s->d_counts + 3;
     hipLaunchKernelGGL(hs_k_sel_subcount, dim3(b.ntiles), dim3(256), 0, s->stream, b);
-    SL_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
     hipLaunchKernelGGL(hs_k_sel_subscan, dim3(1), dim3(1024), 0, s->stream, b);
-    SL_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
     hipLaunchKernelGGL(hs_k_sel_subapply, dim3(b.ntiles), dim3(256), 0, s->stream, b);
-    SL_HIP(hipGetLastError());
-    SL_HIP(hipMemcpyAsync(s->h_counts + 3, s->d_counts + 3, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    SL_HIP(hipStreamSynchronize(s->stream));
+    HS_HIP(hipGetLastError());
+    HS_HIP(hipMemcpyAsync(s->h_counts + 3, s->d_counts + 3, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    HS_HIP(hipStreamSynchronize(s->stream));
     numHaveSub -= s->h_counts[3];
   }
   s->currentPotential = idealPotential;
@@ -264,20 +229,20 @@ int make_maps(hs_selector* s, const float* dI, int dstride, int id, float densit
 }
 
 int check_args(hs_selector* s, float density, float th_factor) {
-  if (!s) return sfail(HS_ERR_INVALID, "null selector");
-  if (!(density > 0.f) || !std::isfinite(density)) return sfail(HS_ERR_INVALID, "density must be > 0");
-  if (!(th_factor > 0.f) || !std::isfinite(th_factor)) return sfail(HS_ERR_INVALID, "thFactor must be > 0");
+  if (!s) return hs::fail(HS_ERR_INVALID, "null selector");
+  if (!(density > 0.f) || !std::isfinite(density)) return hs::fail(HS_ERR_INVALID, "density must be > 0");
+  if (!(th_factor > 0.f) || !std::isfinite(th_factor)) return hs::fail(HS_ERR_INVALID, "thFactor must be > 0");
   if (s->currentPotential < 1 || s->currentPotential > std::max(s->W, s->H))
-    return sfail(HS_ERR_STATE, "potential out of range");
+    return hs::fail(HS_ERR_STATE, "potential out of range");
   return HS_OK;
 }
 
 int finish(hs_selector* s, float* map_out, int* n_selected, int n) {
-  SL_HIP(hipEventRecord(s->e1, s->stream));
+  HS_HIP(hipEventRecord(s->e1, s->stream));
   if (map_out)
-    SL_HIP(hipMemcpyAsync(map_out, s->d_map, (size_t)s->W * s->H * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  SL_HIP(hipStreamSynchronize(s->stream));
-  SL_HIP(hipEventElapsedTime(&s->last_ms, s->e0, s->e1));
+    HS_HIP(hipMemcpyAsync(map_out, s->d_map, (size_t)s->W * s->H * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  HS_HIP(hipStreamSynchronize(s->stream));
+  HS_HIP(hipEventElapsedTime(&s->last_ms, s->e0, s->e1));
   s->have_map = true;
   if (n_selected) *n_selected = n;
   return HS_OK;
@@ -288,67 +253,67 @@ int finish(hs_selector* s, float* map_out, int* n_selected, int n) {
 extern "C" int hs_selector_make_maps(hs_selector* s, int frame_id, const float* dirpyr0, const float* absg0,
                                      const float* absg1, const float* absg2, float density, int recursions_left,
                                      float th_factor, float* map_out, int* n_selected) {
-  SL_TRY(check_args(s, density, th_factor));
-  if (!dirpyr0 || !absg0 || !absg1 || !absg2) return sfail(HS_ERR_INVALID, "null input level");
-  SL_HIP(hipSetDevice(s->device));
+  HS_TRY(check_args(s, density, th_factor));
+  if (!dirpyr0 || !absg0 || !absg1 || !absg2) return hs::fail(HS_ERR_INVALID, "null input level");
+  HS_HIP(hipSetDevice(s->device));
   const size_t area = (size_t)s->W * s->H;
   const size_t n1 = (size_t)(s->W >> 1) * (s->H >> 1), n2 = (size_t)(s->W >> 2) * (s->H >> 2);
-  SL_HIP(hipMemcpyAsync(s->d_dI, dirpyr0, area * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  HS_HIP(hipMemcpyAsync(s->d_dI, dirpyr0, area * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
   // absSquaredGrad[0] feeds makeHists: a new upload invalidates the cached histograms of this frame id only if
   // the caller changes the frame id, as the reference (gradHistFrame)
-  SL_HIP(hipMemcpyAsync(s->d_g[0], absg0, area * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SL_HIP(hipMemcpyAsync(s->d_g[1], absg1, n1 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SL_HIP(hipMemcpyAsync(s->d_g[2], absg2, n2 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SL_HIP(hipEventRecord(s->e0, s->stream));
+  HS_HIP(hipMemcpyAsync(s->d_g[0], absg0, area * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  HS_HIP(hipMemcpyAsync(s->d_g[1], absg1, n1 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  HS_HIP(hipMemcpyAsync(s->d_g[2], absg2, n2 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  HS_HIP(hipEventRecord(s->e0, s->stream));
   s->last_passes = 0;
   s->have_map = false;
   int n = 0;
-  SL_TRY(make_maps(s, s->d_dI, 3, frame_id, density, recursions_left, th_factor, &n));
+  HS_TRY(make_maps(s, s->d_dI, 3, frame_id, density, recursions_left, th_factor, &n));
   return finish(s, map_out, n_selected, n);
 }
 
 extern "C" int hs_selector_make_maps_raw(hs_selector* s, int frame_id, const float* img, float density,
                                          int recursions_left, float th_factor, float* map_out, int* n_selected) {
-  SL_TRY(check_args(s, density, th_factor));
-  if (!img) return sfail(HS_ERR_INVALID, "null image");
-  SL_HIP(hipSetDevice(s->device));
+  HS_TRY(check_args(s, density, th_factor));
+  if (!img) return hs::fail(HS_ERR_INVALID, "null image");
+  HS_HIP(hipSetDevice(s->device));
   const size_t area = (size_t)s->W * s->H;
-  SL_HIP(hipMemcpyAsync(s->d_raw, img, area * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  SL_HIP(hipEventRecord(s->e0, s->stream));
-  SL_HIP(hs_build_dir_pyramid(s->stream, s->d_raw, s->W, s->H, 3, s->d_lvl, s->d_g));
+  HS_HIP(hipMemcpyAsync(s->d_raw, img, area * sizeof(float), hipMemcpyHostToDevice, s->stream));
+  HS_HIP(hipEventRecord(s->e0, s->stream));
+  HS_HIP(hs_build_dir_pyramid(s->stream, s->d_raw, s->W, s->H, 3, s->d_lvl, s->d_g));
   s->last_passes = 0;
   s->have_map = false;
   int n = 0;
-  SL_TRY(make_maps(s, reinterpret_cast<const float*>(s->d_lvl[0]), 4, frame_id, density, recursions_left, th_factor,
+  HS_TRY(make_maps(s, reinterpret_cast<const float*>(s->d_lvl[0]), 4, frame_id, density, recursions_left, th_factor,
                    &n));
   return finish(s, map_out, n_selected, n);
 }
 
 int hs_select_device_map(hs_selector* s, int device, int w, int h, const float** d_map, hipEvent_t* ready) {
-  if (!s) return sfail(HS_ERR_INVALID, "null selector");
-  if (s->device != device) return sfail(HS_ERR_INVALID, "selector and consumer are on different devices");
-  if (s->W != w || s->H != h) return sfail(HS_ERR_INVALID, "selector size differs from the consumer's");
-  if (!s->have_map) return sfail(HS_ERR_STATE, "the selector has made no map (hs_selector_make_maps)");
+  if (!s) return hs::fail(HS_ERR_INVALID, "null selector");
+  if (s->device != device) return hs::fail(HS_ERR_INVALID, "selector and consumer are on different devices");
+  if (s->W != w || s->H != h) return hs::fail(HS_ERR_INVALID, "selector size differs from the consumer's");
+  if (!s->have_map) return hs::fail(HS_ERR_STATE, "the selector has made no map (hs_selector_make_maps)");
   *d_map = s->d_map;
   *ready = s->e1;
   return HS_OK;
 }
 
 extern "C" int hs_selector_get_potential(hs_selector* s, int* potential) {
-  if (!s || !potential) return sfail(HS_ERR_INVALID, "null argument");
+  if (!s || !potential) return hs::fail(HS_ERR_INVALID, "null argument");
   *potential = s->currentPotential;
   return HS_OK;
 }
 
 extern "C" int hs_selector_set_potential(hs_selector* s, int potential) {
-  if (!s) return sfail(HS_ERR_INVALID, "null selector");
-  if (potential < 1) return sfail(HS_ERR_INVALID, "potential must be >= 1");
+  if (!s) return hs::fail(HS_ERR_INVALID, "null selector");
+  if (potential < 1) return hs::fail(HS_ERR_INVALID, "potential must be >= 1");
   s->currentPotential = potential;
   return HS_OK;
 }
 
 extern "C" int hs_selector_last_stats(hs_selector* s, double* ms, int* passes) {
-  if (!s) return sfail(HS_ERR_INVALID, "null selector");
+  if (!s) return hs::fail(HS_ERR_INVALID, "null selector");
   if (ms) *ms = s->last_ms;
   if (passes) *passes = s->last_passes;
   return HS_OK;

@@ -12,6 +12,7 @@
 
 #include "../../include/hs_ba.h"
 #include "../../include/hs_trace.h"
+#include "hs_host.h"
 #include "hs_trace_kernels.h"
 #include "hs_pyr_kernels.h"
 #include "../../include/hs_undist.h"
@@ -22,33 +23,9 @@
 #define HS_MAXF_ACT 8                        // activation window (nF <= 8 keyframes)
 #define HS_ACT_LDS_MAP_MAX (156 * 1024)     // level-1 distance map in LDS up to this size
 
-namespace hs {
-extern thread_local std::string g_err;
-}
-
-namespace {
-int cfail(int code, const std::string& msg) {
-  hs::g_err = msg;
-  return code;
-}
-}  // namespace
-
-#define TR_TRY(x)        \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-#define TR_HIP(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) return cfail(HS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-struct hs_tracer {
+struct hs_tracer : hs::Device {
   hs_params P;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hs::Pool pool;
   int W = 0, H = 0, cap = 0, n = 0;
   float4* d_host_img[HS_TRC_MAXHOST] = {nullptr};
   const float4** d_host_tab = nullptr;
@@ -87,16 +64,16 @@ struct hs_tracer {
 static int upload_img(hs_tracer* t, float4* dst, const float* src) {
   const size_t n = (size_t)t->W * t->H;
   std::vector<float4> tex(n);
-  for (size_t i = 0; i < n; i++) tex[i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0.f);
-  TR_HIP(hipMemcpyAsync(dst, tex.data(), n * sizeof(float4), hipMemcpyHostToDevice, t->stream));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  hs::texels_from_triplets(tex.data(), src, n);
+  HS_HIP(hipMemcpyAsync(dst, tex.data(), n * sizeof(float4), hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipStreamSynchronize(t->stream));
   return HS_OK;
 }
 
 static int sync_stats(hs_tracer* t) {
   if (!t->stats_pending) return HS_OK;
-  TR_HIP(hipStreamSynchronize(t->stream));
-  TR_HIP(hipEventElapsedTime(&t->last_ms, t->e0, t->e1));
+  HS_HIP(hipStreamSynchronize(t->stream));
+  HS_HIP(hipEventElapsedTime(&t->last_ms, t->e0, t->e1));
   long long st = 0;
   memcpy(&st, t->h_counts + 6, sizeof(st));
   t->last_steps = st;
@@ -128,168 +105,155 @@ static int launch_ctor(hs_tracer* t, int first, int n) {
   a.uv = t->d_uv;
   a.interval = t->d_interval;
   hipLaunchKernelGGL(hs_k_imm_ctor, dim3((n + 255) / 256), dim3(256), 0, t->stream, a);
-  TR_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   return HS_OK;
 }
 
 extern "C" {
 
 int hs_tracer_create(hs_tracer** out, const hs_params* params, int device_id, int width, int height, int capacity) {
-  if (!out) return cfail(HS_ERR_INVALID, "null out");
+  if (!out) return hs::fail(HS_ERR_INVALID, "null out");
   *out = nullptr;
-  if (width < 16 || height < 16 || capacity < 1) return cfail(HS_ERR_INVALID, "bad size / capacity");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return cfail(HS_ERR_HIP, "no HIP device");
-  if (device_id < 0 || device_id >= ndev) return cfail(HS_ERR_INVALID, "bad device id");
+  if (width < 16 || height < 16 || capacity < 1) return hs::fail(HS_ERR_INVALID, "bad size / capacity");
+  HS_TRY(hs::check_device(device_id));
   hs_tracer* t = new hs_tracer();
   if (params) t->P = *params;
   else hs_params_default(&t->P);
-  t->device = device_id;
   t->W = width;
   t->H = height;
   t->cap = capacity;
-  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&t->e0) != hipSuccess || hipEventCreate(&t->e1) != hipSuccess) {
-    delete t;
-    return cfail(HS_ERR_HIP, "stream / event creation failed");
-  }
   const size_t c = capacity;
-  TR_HIP(hipMalloc((void**)&t->d_new, (size_t)width * height * sizeof(float4)));
-  TR_HIP(hipMalloc((void**)&t->d_host_tab, sizeof(float4*) * HS_TRC_MAXHOST));
-  TR_HIP(hipMemsetAsync(t->d_host_tab, 0, sizeof(float4*) * HS_TRC_MAXHOST, t->stream));  // the kernels' stream
-  TR_HIP(hipMalloc((void**)&t->d_hosts, sizeof(hs_trace_host) * HS_TRC_MAXHOST));
-  TR_HIP(hipMalloc((void**)&t->d_host, sizeof(int) * c));
-  TR_HIP(hipMalloc((void**)&t->d_u, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_v, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_color, sizeof(float) * 8 * c));
-  TR_HIP(hipMalloc((void**)&t->d_weights, sizeof(float) * 8 * c));
-  TR_HIP(hipMalloc((void**)&t->d_gradH, sizeof(float) * 4 * c));
-  TR_HIP(hipMalloc((void**)&t->d_energyTH, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_quality, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_idmin, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_idmax, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_uv, sizeof(float) * 2 * c));
-  TR_HIP(hipMalloc((void**)&t->d_interval, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_status, c));
-  TR_HIP(hipMalloc((void**)&t->d_steps, sizeof(int) * c));
-  TR_HIP(hipMalloc((void**)&t->d_type, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_counts, sizeof(int) * 8));
-  TR_HIP(hipHostMalloc((void**)&t->h_counts, sizeof(int) * 8));
-  *out = t;
-  return HS_OK;
+  const int rc = [&]() -> int {
+    hs::Pool& m = t->pool;
+    HS_TRY(t->open(device_id));
+    HS_TRY(m.alloc(&t->d_new, (size_t)width * height));
+    HS_TRY(m.alloc_zero(&t->d_host_tab, HS_TRC_MAXHOST, t->stream));  // the kernels' stream
+    HS_TRY(m.alloc(&t->d_hosts, HS_TRC_MAXHOST));
+    HS_TRY(m.alloc(&t->d_host, c));
+    HS_TRY(m.alloc(&t->d_u, c));
+    HS_TRY(m.alloc(&t->d_v, c));
+    HS_TRY(m.alloc(&t->d_color, 8 * c));
+    HS_TRY(m.alloc(&t->d_weights, 8 * c));
+    HS_TRY(m.alloc(&t->d_gradH, 4 * c));
+    HS_TRY(m.alloc(&t->d_energyTH, c));
+    HS_TRY(m.alloc(&t->d_quality, c));
+    HS_TRY(m.alloc(&t->d_idmin, c));
+    HS_TRY(m.alloc(&t->d_idmax, c));
+    HS_TRY(m.alloc(&t->d_uv, 2 * c));
+    HS_TRY(m.alloc(&t->d_interval, c));
+    HS_TRY(m.alloc(&t->d_status, c));
+    HS_TRY(m.alloc(&t->d_steps, c));
+    HS_TRY(m.alloc(&t->d_type, c));
+    HS_TRY(m.alloc(&t->d_counts, 8));
+    HS_TRY(m.pinned(&t->h_counts, 8));
+    return HS_OK;
+  }();
+  if (rc) hs_tracer_destroy(t);
+  else *out = t;
+  return rc;
 }
 
 void hs_tracer_destroy(hs_tracer* t) {
   if (!t) return;
   (void)hipSetDevice(t->device);
   if (t->stream) (void)hipStreamSynchronize(t->stream);
-  for (auto* p : t->d_host_img) (void)hipFree(p);
-  void* bufs[] = {t->d_host_tab, t->d_new, t->d_hosts, t->d_host, t->d_u, t->d_v, t->d_color, t->d_weights,
-                  t->d_gradH, t->d_energyTH, t->d_quality, t->d_idmin, t->d_idmax, t->d_uv, t->d_interval,
-                  t->d_status, t->d_steps, t->d_counts, t->d_raw, t->d_type, t->d_dist, t->d_list_a,
-                  t->d_list_b, t->d_act_cnt, t->d_act_frames, t->d_act_pairs, t->d_frame_of_slot, t->d_order,
-                  t->d_cell, t->d_toopt, t->d_act_seeds, t->d_cand, t->d_action, t->d_res_in, t->d_frac, t->d_thr,
-                  t->d_act_idepth, t->d_ap_frame, t->d_ap_u, t->d_ap_v, t->d_ap_id};
-  for (void* b : bufs) (void)hipFree(b);
-  (void)hipHostFree(t->h_counts);
-  if (t->e0) (void)hipEventDestroy(t->e0);
-  if (t->e1) (void)hipEventDestroy(t->e1);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
+  t->pool.release_all();
+  t->close();
   delete t;
 }
 
 int hs_tracer_set_host_image(hs_tracer* t, int slot, const float* img) {
-  if (!t || !img) return cfail(HS_ERR_INVALID, "null argument");
-  if (slot < 0 || slot >= HS_TRC_MAXHOST) return cfail(HS_ERR_INVALID, "host slot out of range");
-  TR_HIP(hipSetDevice(t->device));
+  if (!t || !img) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (slot < 0 || slot >= HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "host slot out of range");
+  HS_HIP(hipSetDevice(t->device));
   if (!t->d_host_img[slot]) {
-    TR_HIP(hipMalloc((void**)&t->d_host_img[slot], (size_t)t->W * t->H * sizeof(float4)));
-    TR_HIP(hipMemcpyAsync(t->d_host_tab + slot, &t->d_host_img[slot], sizeof(float4*), hipMemcpyHostToDevice,
+    HS_TRY(t->pool.alloc(&t->d_host_img[slot], (size_t)t->W * t->H));
+    HS_HIP(hipMemcpyAsync(t->d_host_tab + slot, &t->d_host_img[slot], sizeof(float4*), hipMemcpyHostToDevice,
                           t->stream));
   }
   return upload_img(t, t->d_host_img[slot], img);
 }
 
 int hs_tracer_clear(hs_tracer* t) {
-  if (!t) return cfail(HS_ERR_INVALID, "null tracer");
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
   t->n = 0;
   t->max_host = -1;
   return HS_OK;
 }
 
 int hs_tracer_add_points(hs_tracer* t, int n, const int* host, const float* u, const float* v) {
-  if (!t || (n > 0 && (!host || !u || !v))) return cfail(HS_ERR_INVALID, "null argument");
-  if (n < 0 || t->n + n > t->cap) return cfail(HS_ERR_INVALID, "point capacity exceeded");
+  if (!t || (n > 0 && (!host || !u || !v))) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (n < 0 || t->n + n > t->cap) return hs::fail(HS_ERR_INVALID, "point capacity exceeded");
   if (n == 0) return HS_OK;
   for (int i = 0; i < n; i++) {
     // the ctor's BiLin taps reach 2 px around (u, v) plus one texel: reject points whose pattern leaves the image
     if (host[i] < 0 || host[i] >= HS_TRC_MAXHOST || !t->d_host_img[host[i]])
-      return cfail(HS_ERR_INVALID, "point on a host slot without an image");
+      return hs::fail(HS_ERR_INVALID, "point on a host slot without an image");
     if (!(u[i] >= 2 && v[i] >= 2 && u[i] < t->W - 3 && v[i] < t->H - 3))
-      return cfail(HS_ERR_INVALID, "immature point too close to the image border");
+      return hs::fail(HS_ERR_INVALID, "immature point too close to the image border");
   }
-  TR_HIP(hipSetDevice(t->device));
+  HS_HIP(hipSetDevice(t->device));
   const int f = t->n;
-  TR_HIP(hipMemcpyAsync(t->d_host + f, host, sizeof(int) * n, hipMemcpyHostToDevice, t->stream));
-  TR_HIP(hipMemcpyAsync(t->d_u + f, u, sizeof(float) * n, hipMemcpyHostToDevice, t->stream));
-  TR_HIP(hipMemcpyAsync(t->d_v + f, v, sizeof(float) * n, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipMemcpyAsync(t->d_host + f, host, sizeof(int) * n, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipMemcpyAsync(t->d_u + f, u, sizeof(float) * n, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipMemcpyAsync(t->d_v + f, v, sizeof(float) * n, hipMemcpyHostToDevice, t->stream));
   const std::vector<float> ones(n, 1.f);
-  TR_HIP(hipMemcpyAsync(t->d_type + f, ones.data(), sizeof(float) * n, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipMemcpyAsync(t->d_type + f, ones.data(), sizeof(float) * n, hipMemcpyHostToDevice, t->stream));
   for (int i = 0; i < n; i++) t->max_host = std::max(t->max_host, host[i]);
-  TR_TRY(launch_ctor(t, f, n));
-  TR_HIP(hipStreamSynchronize(t->stream));  // host arrays may go away after return
+  HS_TRY(launch_ctor(t, f, n));
+  HS_HIP(hipStreamSynchronize(t->stream));  // host arrays may go away after return
   t->n += n;
   return HS_OK;
 }
 
 int hs_tracer_add_keys(hs_tracer* t, hs_extractor* e, int slot, int* n_added) {
-  if (!t || !e) return cfail(HS_ERR_INVALID, "null argument");
+  if (!t || !e) return hs::fail(HS_ERR_INVALID, "null argument");
   if (slot < 0 || slot >= HS_TRC_MAXHOST || !t->d_host_img[slot])
-    return cfail(HS_ERR_INVALID, "keys on a host slot without an image");
+    return hs::fail(HS_ERR_INVALID, "keys on a host slot without an image");
   int dev = 0, w = 0, h = 0, n = 0;
   const float *d_x = nullptr, *d_y = nullptr;
   hipEvent_t ready = nullptr;
   hs_extract_keys(e, &dev, &w, &h, &n, &d_x, &d_y, &ready);
-  if (dev != t->device) return cfail(HS_ERR_INVALID, "extractor and tracer are on different devices");
-  if (w != t->W || h != t->H) return cfail(HS_ERR_INVALID, "extractor size differs from the tracer's");
-  if (t->n + n > t->cap) return cfail(HS_ERR_INVALID, "point capacity exceeded");
+  if (dev != t->device) return hs::fail(HS_ERR_INVALID, "extractor and tracer are on different devices");
+  if (w != t->W || h != t->H) return hs::fail(HS_ERR_INVALID, "extractor size differs from the tracer's");
+  if (t->n + n > t->cap) return hs::fail(HS_ERR_INVALID, "point capacity exceeded");
   if (n_added) *n_added = n;
   if (n == 0) return HS_OK;
-  TR_HIP(hipSetDevice(t->device));
+  HS_HIP(hipSetDevice(t->device));
   const int f = t->n;
   // keys lie >= 19 px from every edge (include/hs_extract.h): add_points' border rule holds by construction
-  TR_HIP(hipStreamWaitEvent(t->stream, ready, 0));
-  TR_HIP(hipMemcpyAsync(t->d_u + f, d_x, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
-  TR_HIP(hipMemcpyAsync(t->d_v + f, d_y, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
-  TR_HIP(hs_extract_keys_consumed(e, t->stream));
-  TR_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_host + f), slot, n, t->stream));
-  TR_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_type + f), 0x3f800000, n, t->stream));  // my_type 1.f
+  HS_HIP(hipStreamWaitEvent(t->stream, ready, 0));
+  HS_HIP(hipMemcpyAsync(t->d_u + f, d_x, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
+  HS_HIP(hipMemcpyAsync(t->d_v + f, d_y, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
+  HS_HIP(hs_extract_keys_consumed(e, t->stream));
+  HS_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_host + f), slot, n, t->stream));
+  HS_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_type + f), 0x3f800000, n, t->stream));  // my_type 1.f
   t->max_host = std::max(t->max_host, slot);
-  TR_TRY(launch_ctor(t, f, n));
+  HS_TRY(launch_ctor(t, f, n));
   t->n += n;
   return HS_OK;
 }
 
 int hs_tracer_set_state(hs_tracer* t, const float* idepth_min, const float* idepth_max, const float* quality,
                         const uint8_t* status, const float* interval) {
-  if (!t) return cfail(HS_ERR_INVALID, "null tracer");
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
   if (status)
     for (int i = 0; i < t->n; i++)
-      if (status[i] > HS_IPS_UNINITIALIZED) return cfail(HS_ERR_INVALID, "bad ImmaturePointStatus");
-  TR_HIP(hipSetDevice(t->device));
+      if (status[i] > HS_IPS_UNINITIALIZED) return hs::fail(HS_ERR_INVALID, "bad ImmaturePointStatus");
+  HS_HIP(hipSetDevice(t->device));
   const size_t n = t->n;
-  if (idepth_min) TR_HIP(hipMemcpyAsync(t->d_idmin, idepth_min, 4 * n, hipMemcpyHostToDevice, t->stream));
-  if (idepth_max) TR_HIP(hipMemcpyAsync(t->d_idmax, idepth_max, 4 * n, hipMemcpyHostToDevice, t->stream));
-  if (quality) TR_HIP(hipMemcpyAsync(t->d_quality, quality, 4 * n, hipMemcpyHostToDevice, t->stream));
-  if (status) TR_HIP(hipMemcpyAsync(t->d_status, status, n, hipMemcpyHostToDevice, t->stream));
-  if (interval) TR_HIP(hipMemcpyAsync(t->d_interval, interval, 4 * n, hipMemcpyHostToDevice, t->stream));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  if (idepth_min) HS_HIP(hipMemcpyAsync(t->d_idmin, idepth_min, 4 * n, hipMemcpyHostToDevice, t->stream));
+  if (idepth_max) HS_HIP(hipMemcpyAsync(t->d_idmax, idepth_max, 4 * n, hipMemcpyHostToDevice, t->stream));
+  if (quality) HS_HIP(hipMemcpyAsync(t->d_quality, quality, 4 * n, hipMemcpyHostToDevice, t->stream));
+  if (status) HS_HIP(hipMemcpyAsync(t->d_status, status, n, hipMemcpyHostToDevice, t->stream));
+  if (interval) HS_HIP(hipMemcpyAsync(t->d_interval, interval, 4 * n, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipStreamSynchronize(t->stream));
   return HS_OK;
 }
 
 int hs_tracer_set_frame(hs_tracer* t, const float* img) {
-  if (!t || !img) return cfail(HS_ERR_INVALID, "null argument");
-  TR_HIP(hipSetDevice(t->device));
+  if (!t || !img) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
   int rc = upload_img(t, t->d_new, img);
   if (rc) return rc;
   t->have_frame = true;
@@ -297,39 +261,39 @@ int hs_tracer_set_frame(hs_tracer* t, const float* img) {
 }
 
 int hs_tracer_set_frame_raw(hs_tracer* t, const float* img) {
-  if (!t || !img) return cfail(HS_ERR_INVALID, "null argument");
-  TR_HIP(hipSetDevice(t->device));
-  if (!t->d_raw) TR_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
-  TR_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
+  if (!t || !img) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
+  if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
+  HS_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
   float4* lv[1] = {t->d_new};
-  TR_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
+  HS_HIP(hipStreamSynchronize(t->stream));
   t->have_frame = true;
   return HS_OK;
 }
 
 int hs_tracer_set_frame_u8(hs_tracer* t, hs_undistorter* u, const uint8_t* raw) {
-  if (!t || !u || !raw) return cfail(HS_ERR_INVALID, "null argument");
-  TR_TRY(hs_undist_match(u, t->device, t->W, t->H));
-  TR_HIP(hipSetDevice(t->device));
-  if (!t->d_raw) TR_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
-  TR_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
+  if (!t || !u || !raw) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(hs_undist_match(u, t->device, t->W, t->H));
+  HS_HIP(hipSetDevice(t->device));
+  if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
+  HS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
   float4* lv[1] = {t->d_new};
-  TR_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
+  HS_HIP(hipStreamSynchronize(t->stream));
   t->have_frame = true;
   return HS_OK;
 }
 
 int hs_tracer_trace(hs_tracer* t, int n_hosts, const hs_trace_host* hosts, int counts6[6]) {
-  if (!t || (n_hosts > 0 && !hosts)) return cfail(HS_ERR_INVALID, "null argument");
-  if (n_hosts < 0 || n_hosts > HS_TRC_MAXHOST) return cfail(HS_ERR_INVALID, "n_hosts out of range");
-  if (!t->have_frame) return cfail(HS_ERR_STATE, "no frame to trace on (hs_tracer_set_frame)");
-  TR_HIP(hipSetDevice(t->device));
+  if (!t || (n_hosts > 0 && !hosts)) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (n_hosts < 0 || n_hosts > HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "n_hosts out of range");
+  if (!t->have_frame) return hs::fail(HS_ERR_STATE, "no frame to trace on (hs_tracer_set_frame)");
+  HS_HIP(hipSetDevice(t->device));
   if (t->n > 0) {
     // every point's host slot must have its (KRKi, Kt, aff)
-    if (t->max_host >= n_hosts) return cfail(HS_ERR_INVALID, "a point's host slot has no hs_trace_host entry");
-    TR_HIP(hipMemcpyAsync(t->d_hosts, hosts, sizeof(hs_trace_host) * n_hosts, hipMemcpyHostToDevice, t->stream));
+    if (t->max_host >= n_hosts) return hs::fail(HS_ERR_INVALID, "a point's host slot has no hs_trace_host entry");
+    HS_HIP(hipMemcpyAsync(t->d_hosts, hosts, sizeof(hs_trace_host) * n_hosts, hipMemcpyHostToDevice, t->stream));
   }
   HsTraceArgs a;
   a.n = t->n;
@@ -360,64 +324,64 @@ int hs_tracer_trace(hs_tracer* t, int n_hosts, const hs_trace_host* hosts, int c
   a.extraSlackOnTH = t->P.trace_extraSlackOnTH;
   a.minTraceTestRadius = t->P.minTraceTestRadius;
   a.GNIterations = t->P.trace_GNIterations;
-  TR_HIP(hipEventRecord(t->e0, t->stream));
+  HS_HIP(hipEventRecord(t->e0, t->stream));
   if (t->n > 0) {
     hipLaunchKernelGGL(hs_k_trace_on, dim3((t->n + 3) / 4), dim3(256), 0, t->stream, a);
-    TR_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
-  TR_HIP(hipEventRecord(t->e1, t->stream));
+  HS_HIP(hipEventRecord(t->e1, t->stream));
   hipLaunchKernelGGL(hs_k_trace_count, dim3(1), dim3(1024), 0, t->stream, t->n, t->d_status, t->d_steps,
                      t->d_counts);
-  TR_HIP(hipGetLastError());
-  TR_HIP(hipMemcpyAsync(t->h_counts, t->d_counts, sizeof(int) * 8, hipMemcpyDeviceToHost, t->stream));
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(t->h_counts, t->d_counts, sizeof(int) * 8, hipMemcpyDeviceToHost, t->stream));
   t->stats_pending = true;
   if (!counts6) return HS_OK;  // asynchronous: hs_tracer_last_stats / get_points synchronise
-  TR_TRY(sync_stats(t));
+  HS_TRY(sync_stats(t));
   for (int k = 0; k < 6; k++) counts6[k] = t->h_counts[k];
   return HS_OK;
 }
 
 int hs_tracer_get_points(hs_tracer* t, int* n, uint8_t* status, float* idepth_min, float* idepth_max, float* quality,
                          float* uv, float* interval, float* energyTH, float* color, float* weights, float* gradH) {
-  if (!t) return cfail(HS_ERR_INVALID, "null tracer");
-  TR_HIP(hipSetDevice(t->device));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipStreamSynchronize(t->stream));
   const size_t m = t->n;
   if (n) *n = t->n;
-  if (status) TR_HIP(hipMemcpy(status, t->d_status, m, hipMemcpyDeviceToHost));
-  if (idepth_min) TR_HIP(hipMemcpy(idepth_min, t->d_idmin, 4 * m, hipMemcpyDeviceToHost));
-  if (idepth_max) TR_HIP(hipMemcpy(idepth_max, t->d_idmax, 4 * m, hipMemcpyDeviceToHost));
-  if (quality) TR_HIP(hipMemcpy(quality, t->d_quality, 4 * m, hipMemcpyDeviceToHost));
-  if (uv) TR_HIP(hipMemcpy(uv, t->d_uv, 8 * m, hipMemcpyDeviceToHost));
-  if (interval) TR_HIP(hipMemcpy(interval, t->d_interval, 4 * m, hipMemcpyDeviceToHost));
-  if (energyTH) TR_HIP(hipMemcpy(energyTH, t->d_energyTH, 4 * m, hipMemcpyDeviceToHost));
-  if (color) TR_HIP(hipMemcpy(color, t->d_color, 32 * m, hipMemcpyDeviceToHost));
-  if (weights) TR_HIP(hipMemcpy(weights, t->d_weights, 32 * m, hipMemcpyDeviceToHost));
-  if (gradH) TR_HIP(hipMemcpy(gradH, t->d_gradH, 16 * m, hipMemcpyDeviceToHost));
+  if (status) HS_HIP(hipMemcpy(status, t->d_status, m, hipMemcpyDeviceToHost));
+  if (idepth_min) HS_HIP(hipMemcpy(idepth_min, t->d_idmin, 4 * m, hipMemcpyDeviceToHost));
+  if (idepth_max) HS_HIP(hipMemcpy(idepth_max, t->d_idmax, 4 * m, hipMemcpyDeviceToHost));
+  if (quality) HS_HIP(hipMemcpy(quality, t->d_quality, 4 * m, hipMemcpyDeviceToHost));
+  if (uv) HS_HIP(hipMemcpy(uv, t->d_uv, 8 * m, hipMemcpyDeviceToHost));
+  if (interval) HS_HIP(hipMemcpy(interval, t->d_interval, 4 * m, hipMemcpyDeviceToHost));
+  if (energyTH) HS_HIP(hipMemcpy(energyTH, t->d_energyTH, 4 * m, hipMemcpyDeviceToHost));
+  if (color) HS_HIP(hipMemcpy(color, t->d_color, 32 * m, hipMemcpyDeviceToHost));
+  if (weights) HS_HIP(hipMemcpy(weights, t->d_weights, 32 * m, hipMemcpyDeviceToHost));
+  if (gradH) HS_HIP(hipMemcpy(gradH, t->d_gradH, 16 * m, hipMemcpyDeviceToHost));
   return HS_OK;
 }
 
 int hs_tracer_last_stats(hs_tracer* t, double* ms, long long* search_steps) {
-  if (!t) return cfail(HS_ERR_INVALID, "null tracer");
-  TR_HIP(hipSetDevice(t->device));
-  TR_TRY(sync_stats(t));
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(sync_stats(t));
   if (ms) *ms = t->last_ms;
   if (search_steps) *search_steps = t->last_steps;
   return HS_OK;
 }
 
 int hs_tracer_reinit(hs_tracer* t) {
-  if (!t) return cfail(HS_ERR_INVALID, "null tracer");
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
   if (t->n == 0) return HS_OK;
-  TR_HIP(hipSetDevice(t->device));
+  HS_HIP(hipSetDevice(t->device));
   return launch_ctor(t, 0, t->n);
 }
 
 int hs_tracer_set_types(hs_tracer* t, const float* my_type) {
-  if (!t || (t->n > 0 && !my_type)) return cfail(HS_ERR_INVALID, "null argument");
-  TR_HIP(hipSetDevice(t->device));
-  TR_HIP(hipMemcpyAsync(t->d_type, my_type, sizeof(float) * t->n, hipMemcpyHostToDevice, t->stream));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  if (!t || (t->n > 0 && !my_type)) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipMemcpyAsync(t->d_type, my_type, sizeof(float) * t->n, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hipStreamSynchronize(t->stream));
   return HS_OK;
 }
 
@@ -426,38 +390,40 @@ static int act_alloc(hs_tracer* t) {
   t->w1 = t->W >> 1;
   t->h1 = t->H >> 1;
   const size_t wh1 = (size_t)t->w1 * t->h1, c = t->cap;
-  TR_HIP(hipMalloc((void**)&t->d_dist, (wh1 + 3) & ~(size_t)3));
-  TR_HIP(hipMalloc((void**)&t->d_list_a, sizeof(int) * wh1));
-  TR_HIP(hipMalloc((void**)&t->d_list_b, sizeof(int) * wh1));
-  TR_HIP(hipMalloc((void**)&t->d_act_cnt, sizeof(int) * 2));
-  TR_HIP(hipMalloc((void**)&t->d_act_frames, sizeof(hs_act_frame) * HS_MAXF_ACT));
-  TR_HIP(hipMalloc((void**)&t->d_act_pairs, sizeof(hs_act_pair) * HS_MAXF_ACT * HS_MAXF_ACT));
-  TR_HIP(hipMalloc((void**)&t->d_frame_of_slot, sizeof(int) * HS_TRC_MAXHOST));
-  TR_HIP(hipMalloc((void**)&t->d_order, sizeof(int) * c));
-  TR_HIP(hipMalloc((void**)&t->d_cell, sizeof(int) * c));
-  TR_HIP(hipMalloc((void**)&t->d_toopt, sizeof(int) * (c + 64)));  // + the greedy loop's 64 scratch slots
-  TR_HIP(hipMalloc((void**)&t->d_act_seeds, sizeof(int) * 2 * (size_t)c));  // seeds | the select's pending list
-  TR_HIP(hipMalloc((void**)&t->d_cand, c));
-  TR_HIP(hipMalloc((void**)&t->d_action, c));
-  TR_HIP(hipMalloc((void**)&t->d_res_in, c));
-  TR_HIP(hipMalloc((void**)&t->d_frac, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_thr, sizeof(float) * c));
-  TR_HIP(hipMalloc((void**)&t->d_act_idepth, sizeof(float) * c));
+  hs::Pool& m = t->pool;
+  HS_TRY(m.alloc(&t->d_dist, (wh1 + 3) & ~(size_t)3));
+  HS_TRY(m.alloc(&t->d_list_a, wh1));
+  HS_TRY(m.alloc(&t->d_list_b, wh1));
+  HS_TRY(m.alloc(&t->d_act_cnt, 2));
+  HS_TRY(m.alloc(&t->d_act_frames, HS_MAXF_ACT));
+  HS_TRY(m.alloc(&t->d_act_pairs, HS_MAXF_ACT * HS_MAXF_ACT));
+  HS_TRY(m.alloc(&t->d_frame_of_slot, HS_TRC_MAXHOST));
+  HS_TRY(m.alloc(&t->d_order, c));
+  HS_TRY(m.alloc(&t->d_cell, c));
+  HS_TRY(m.alloc(&t->d_toopt, c + 64));  // + the greedy loop's 64 scratch slots
+  HS_TRY(m.alloc(&t->d_act_seeds, 2 * c));  // seeds | the select's pending list
+  HS_TRY(m.alloc(&t->d_cand, c));
+  HS_TRY(m.alloc(&t->d_action, c));
+  HS_TRY(m.alloc(&t->d_res_in, c));
+  HS_TRY(m.alloc(&t->d_frac, c));
+  HS_TRY(m.alloc(&t->d_thr, c));
+  HS_TRY(m.alloc(&t->d_act_idepth, c));
   t->act_ready = true;
   return HS_OK;
 }
 
 static int act_points_alloc(hs_tracer* t, int n) {
   if (n <= t->act_cap) return HS_OK;
-  void* old[] = {t->d_ap_frame, t->d_ap_u, t->d_ap_v, t->d_ap_id};
-  for (void* b : old) TR_HIP(hipFree(b));
-  t->d_ap_frame = nullptr;
-  t->d_ap_u = t->d_ap_v = t->d_ap_id = nullptr;
+  hs::Pool& m = t->pool;
+  m.release(&t->d_ap_frame);
+  m.release(&t->d_ap_u);
+  m.release(&t->d_ap_v);
+  m.release(&t->d_ap_id);
   t->act_cap = 0;
-  TR_HIP(hipMalloc((void**)&t->d_ap_frame, sizeof(int) * n));
-  TR_HIP(hipMalloc((void**)&t->d_ap_u, sizeof(float) * n));
-  TR_HIP(hipMalloc((void**)&t->d_ap_v, sizeof(float) * n));
-  TR_HIP(hipMalloc((void**)&t->d_ap_id, sizeof(float) * n));
+  HS_TRY(m.alloc(&t->d_ap_frame, n));
+  HS_TRY(m.alloc(&t->d_ap_u, n));
+  HS_TRY(m.alloc(&t->d_ap_v, n));
+  HS_TRY(m.alloc(&t->d_ap_id, n));
   t->act_cap = n;
   return HS_OK;
 }
@@ -481,50 +447,50 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
                        const float* act_idepth, int ef_nPoints, float* currentMinActDist, int n_order,
                        const int* order, uint8_t* action, float* idepth, uint8_t* res_in, int* activated,
                        int* n_activated) {
-  if (!t || !K4 || !frames || !pairs || !currentMinActDist) return cfail(HS_ERR_INVALID, "null argument");
-  if (nF < 2 || nF > HS_MAXF_ACT) return cfail(HS_ERR_INVALID, "window size out of range (2..8 keyframes)");
+  if (!t || !K4 || !frames || !pairs || !currentMinActDist) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (nF < 2 || nF > HS_MAXF_ACT) return hs::fail(HS_ERR_INVALID, "window size out of range (2..8 keyframes)");
   if (n_active < 0 || (n_active > 0 && (!act_frame || !act_u || !act_v || !act_idepth)))
-    return cfail(HS_ERR_INVALID, "bad active point arrays");
-  if (!(K4[0] > 0) || !(K4[1] > 0)) return cfail(HS_ERR_INVALID, "bad intrinsics");
+    return hs::fail(HS_ERR_INVALID, "bad active point arrays");
+  if (!(K4[0] > 0) || !(K4[1] > 0)) return hs::fail(HS_ERR_INVALID, "bad intrinsics");
   std::vector<int> fos(HS_TRC_MAXHOST, -1);
   for (int f = 0; f < nF; f++) {
     const int sl = frames[f].slot;
-    if (sl < 0 || sl >= HS_TRC_MAXHOST || !t->d_host_img[sl]) return cfail(HS_ERR_INVALID, "window frame without an image slot");
-    if (fos[sl] >= 0) return cfail(HS_ERR_INVALID, "two window frames on one slot");
+    if (sl < 0 || sl >= HS_TRC_MAXHOST || !t->d_host_img[sl]) return hs::fail(HS_ERR_INVALID, "window frame without an image slot");
+    if (fos[sl] >= 0) return hs::fail(HS_ERR_INVALID, "two window frames on one slot");
     fos[sl] = f;
   }
   for (int i = 0; i < n_active; i++)
-    if (act_frame[i] < 0 || act_frame[i] >= nF) return cfail(HS_ERR_INVALID, "active point on no window frame");
+    if (act_frame[i] < 0 || act_frame[i] >= nF) return hs::fail(HS_ERR_INVALID, "active point on no window frame");
   const int m = order ? n_order : t->n;
   if (order) {
-    if (n_order < 0 || n_order > t->n) return cfail(HS_ERR_INVALID, "bad n_order");
+    if (n_order < 0 || n_order > t->n) return hs::fail(HS_ERR_INVALID, "bad n_order");
     std::vector<char> seen(t->n, 0);
     for (int j = 0; j < n_order; j++) {
-      if (order[j] < 0 || order[j] >= t->n || seen[order[j]]) return cfail(HS_ERR_INVALID, "order is not a subset permutation");
+      if (order[j] < 0 || order[j] >= t->n || seen[order[j]]) return hs::fail(HS_ERR_INVALID, "order is not a subset permutation");
       seen[order[j]] = 1;
     }
   }
-  TR_HIP(hipSetDevice(t->device));
-  TR_TRY(sync_stats(t));
-  TR_TRY(act_alloc(t));
-  TR_TRY(act_points_alloc(t, std::max(1, n_active)));
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(sync_stats(t));
+  HS_TRY(act_alloc(t));
+  HS_TRY(act_points_alloc(t, std::max(1, n_active)));
   update_min_act_dist(t->P, ef_nPoints, *currentMinActDist);
   hipStream_t s = t->stream;
   const int wh1 = t->w1 * t->h1;
-  TR_HIP(hipMemcpyAsync(t->d_act_frames, frames, sizeof(hs_act_frame) * nF, hipMemcpyHostToDevice, s));
-  TR_HIP(hipMemcpyAsync(t->d_act_pairs, pairs, sizeof(hs_act_pair) * nF * nF, hipMemcpyHostToDevice, s));
-  TR_HIP(hipMemcpyAsync(t->d_frame_of_slot, fos.data(), sizeof(int) * HS_TRC_MAXHOST, hipMemcpyHostToDevice, s));
-  if (order && m > 0) TR_HIP(hipMemcpyAsync(t->d_order, order, sizeof(int) * m, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(t->d_act_frames, frames, sizeof(hs_act_frame) * nF, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(t->d_act_pairs, pairs, sizeof(hs_act_pair) * nF * nF, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(t->d_frame_of_slot, fos.data(), sizeof(int) * HS_TRC_MAXHOST, hipMemcpyHostToDevice, s));
+  if (order && m > 0) HS_HIP(hipMemcpyAsync(t->d_order, order, sizeof(int) * m, hipMemcpyHostToDevice, s));
   if (n_active > 0) {
-    TR_HIP(hipMemcpyAsync(t->d_ap_frame, act_frame, sizeof(int) * n_active, hipMemcpyHostToDevice, s));
-    TR_HIP(hipMemcpyAsync(t->d_ap_u, act_u, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
-    TR_HIP(hipMemcpyAsync(t->d_ap_v, act_v, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
-    TR_HIP(hipMemcpyAsync(t->d_ap_id, act_idepth, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_frame, act_frame, sizeof(int) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_u, act_u, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_v, act_v, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_id, act_idepth, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
   }
-  TR_HIP(hipMemsetAsync(t->d_dist, 0xff, (wh1 + 3) & ~3, s));
-  TR_HIP(hipMemsetAsync(t->d_act_cnt, 0, sizeof(int) * 2, s));
-  TR_HIP(hipMemsetAsync(t->d_action, HS_ACT_KEEP, std::max(1, t->n), s));
-  TR_HIP(hipMemsetAsync(t->d_res_in, 0, std::max(1, t->n), s));
+  HS_HIP(hipMemsetAsync(t->d_dist, 0xff, (wh1 + 3) & ~3, s));
+  HS_HIP(hipMemsetAsync(t->d_act_cnt, 0, sizeof(int) * 2, s));
+  HS_HIP(hipMemsetAsync(t->d_action, HS_ACT_KEEP, std::max(1, t->n), s));
+  HS_HIP(hipMemsetAsync(t->d_res_in, 0, std::max(1, t->n), s));
 
   HsActSeedArgs sa;
   sa.n = n_active;
@@ -541,7 +507,7 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   sa.count = t->d_act_cnt;
   if (n_active > 0) {
     hipLaunchKernelGGL(hs_k_act_seed, dim3((n_active + 255) / 256), dim3(256), 0, s, sa);
-    TR_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
   HsActCandArgs ca;
   ca.m = m;
@@ -569,7 +535,7 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   ca.action = t->d_action;
   if (m > 0) {
     hipLaunchKernelGGL(hs_k_act_cand, dim3((m + 255) / 256), dim3(256), 0, s, ca);
-    TR_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
   // makeDistanceMap's growDistBFS over the seeds
   HsActDistArgs ma;
@@ -587,7 +553,7 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   ma.init = t->d_dist;
   ma.out = reinterpret_cast<uint8_t*>(t->d_list_b);
   hipLaunchKernelGGL(hs_k_act_dist, dim3(dist_blocks), dim3(256), 0, s, ma);
-  TR_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   HsActSelectArgs se;
   se.m = m;
   se.w1 = t->w1;
@@ -606,14 +572,15 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   se.toopt = t->d_toopt;
   se.n_toopt = t->d_act_cnt + 1;
   static const bool prof_on = getenv("HS_ACT_PROF") != nullptr;
+  hs::Pool scratch;  // freed on every return path
   long long* d_prof = nullptr;
-  if (prof_on) TR_HIP(hipMalloc((void**)&d_prof, sizeof(long long) * 11));
+  if (prof_on) HS_TRY(scratch.alloc(&d_prof, 11));
   se.prof = d_prof;
   const size_t lds = se.lds_map ? map_bytes : 0;
   if (lds > 65536)
-    TR_HIP(hipFuncSetAttribute((const void*)hs_k_act_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HS_HIP(hipFuncSetAttribute((const void*)hs_k_act_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(hs_k_act_select, dim3(1), dim3(1024), lds, s, se);
-  TR_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   HsActDistArgs fa = ma;  // the map the greedy loop leaves
   fa.mode = 1;
   fa.seeds = se.seeds;
@@ -621,15 +588,14 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   fa.init = ma.out;
   fa.out = t->d_dist;
   hipLaunchKernelGGL(hs_k_act_dist, dim3(dist_blocks), dim3(256), 0, s, fa);
-  TR_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   int cnt[2] = {0, 0};
-  TR_HIP(hipMemcpyAsync(cnt, t->d_act_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
-  TR_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(cnt, t->d_act_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   const int n_toopt = cnt[1];
   if (d_prof) {
     long long pr[11];
-    TR_HIP(hipMemcpy(pr, d_prof, sizeof(pr), hipMemcpyDeviceToHost));
-    TR_HIP(hipFree(d_prof));
+    HS_HIP(hipMemcpy(pr, d_prof, sizeof(pr), hipMemcpyDeviceToHost));
     fprintf(stderr, "hs act prof: prologue %.1f us, greedy %.1f us (decisions %.1f, folds %.1f of which border %.1f; "
             "wall_clock64 @100 MHz), %d selected; %lld batches, %lld seed patches of radius %lld; core clock %.0f MHz\n",
             (pr[1] - pr[0]) * 1e-2, (pr[2] - pr[1]) * 1e-2, pr[8] * 1e-2, pr[9] * 1e-2, pr[10] * 1e-2, n_toopt, pr[3],
@@ -668,16 +634,16 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
     oa.idepth_out = t->d_act_idepth;
     oa.res_in = t->d_res_in;
     hipLaunchKernelGGL(hs_k_act_optimize, dim3((n_toopt + 3) / 4), dim3(256), 0, s, oa);
-    TR_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
   const size_t n = t->n;
   std::vector<uint8_t> act(std::max<size_t>(1, n));
   std::vector<int> toopt(std::max(1, n_toopt));
-  TR_HIP(hipMemcpyAsync(act.data(), t->d_action, n, hipMemcpyDeviceToHost, s));
-  if (n_toopt > 0) TR_HIP(hipMemcpyAsync(toopt.data(), t->d_toopt, sizeof(int) * n_toopt, hipMemcpyDeviceToHost, s));
-  if (idepth && n) TR_HIP(hipMemcpyAsync(idepth, t->d_act_idepth, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-  if (res_in && n) TR_HIP(hipMemcpyAsync(res_in, t->d_res_in, n, hipMemcpyDeviceToHost, s));
-  TR_HIP(hipStreamSynchronize(s));
+  HS_HIP(hipMemcpyAsync(act.data(), t->d_action, n, hipMemcpyDeviceToHost, s));
+  if (n_toopt > 0) HS_HIP(hipMemcpyAsync(toopt.data(), t->d_toopt, sizeof(int) * n_toopt, hipMemcpyDeviceToHost, s));
+  if (idepth && n) HS_HIP(hipMemcpyAsync(idepth, t->d_act_idepth, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+  if (res_in && n) HS_HIP(hipMemcpyAsync(res_in, t->d_res_in, n, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
   if (action && n) memcpy(action, act.data(), n);
   int na = 0;
   for (int k = 0; k < n_toopt; k++)
@@ -693,13 +659,13 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
 }
 
 int hs_tracer_get_distance_map(hs_tracer* t, float* dist) {
-  if (!t || !dist) return cfail(HS_ERR_INVALID, "null argument");
-  if (!t->act_ready) return cfail(HS_ERR_STATE, "no activation has run");
-  TR_HIP(hipSetDevice(t->device));
+  if (!t || !dist) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (!t->act_ready) return hs::fail(HS_ERR_STATE, "no activation has run");
+  HS_HIP(hipSetDevice(t->device));
   const size_t wh1 = (size_t)t->w1 * t->h1;
   std::vector<uint8_t> b(wh1);
-  TR_HIP(hipStreamSynchronize(t->stream));
-  TR_HIP(hipMemcpy(b.data(), t->d_dist, wh1, hipMemcpyDeviceToHost));
+  HS_HIP(hipStreamSynchronize(t->stream));
+  HS_HIP(hipMemcpy(b.data(), t->d_dist, wh1, hipMemcpyDeviceToHost));
   for (size_t i = 0; i < wh1; i++) dist[i] = b[i] == 255 ? 1000.f : (float)b[i];
   return HS_OK;
 }
@@ -709,41 +675,41 @@ extern "C++" template <typename T>
 static int compact_array(hs_tracer* t, T* d, int per, const std::vector<int>& keep_idx) {
   const size_t n = t->n;
   std::vector<T> h(n * per), o(keep_idx.size() * per);
-  if (n) TR_HIP(hipMemcpy(h.data(), d, sizeof(T) * n * per, hipMemcpyDeviceToHost));
+  if (n) HS_HIP(hipMemcpy(h.data(), d, sizeof(T) * n * per, hipMemcpyDeviceToHost));
   for (size_t k = 0; k < keep_idx.size(); k++)
     for (int c = 0; c < per; c++) o[k * per + c] = h[(size_t)keep_idx[k] * per + c];
   if (!o.empty()) {  // on the kernels' stream; o lives until the copy has landed
-    TR_HIP(hipMemcpyAsync(d, o.data(), sizeof(T) * o.size(), hipMemcpyHostToDevice, t->stream));
-    TR_HIP(hipStreamSynchronize(t->stream));
+    HS_HIP(hipMemcpyAsync(d, o.data(), sizeof(T) * o.size(), hipMemcpyHostToDevice, t->stream));
+    HS_HIP(hipStreamSynchronize(t->stream));
   }
   return HS_OK;
 }
 
 int hs_tracer_compact(hs_tracer* t, const uint8_t* keep) {
-  if (!t || (t->n > 0 && !keep)) return cfail(HS_ERR_INVALID, "null argument");
-  TR_HIP(hipSetDevice(t->device));
-  TR_TRY(sync_stats(t));
-  TR_HIP(hipStreamSynchronize(t->stream));
+  if (!t || (t->n > 0 && !keep)) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(sync_stats(t));
+  HS_HIP(hipStreamSynchronize(t->stream));
   std::vector<int> idx;
   for (int i = 0; i < t->n; i++)
     if (keep[i]) idx.push_back(i);
-  TR_TRY(compact_array(t, t->d_host, 1, idx));
-  TR_TRY(compact_array(t, t->d_u, 1, idx));
-  TR_TRY(compact_array(t, t->d_v, 1, idx));
-  TR_TRY(compact_array(t, t->d_color, 8, idx));
-  TR_TRY(compact_array(t, t->d_weights, 8, idx));
-  TR_TRY(compact_array(t, t->d_gradH, 4, idx));
-  TR_TRY(compact_array(t, t->d_energyTH, 1, idx));
-  TR_TRY(compact_array(t, t->d_quality, 1, idx));
-  TR_TRY(compact_array(t, t->d_idmin, 1, idx));
-  TR_TRY(compact_array(t, t->d_idmax, 1, idx));
-  TR_TRY(compact_array(t, t->d_uv, 2, idx));
-  TR_TRY(compact_array(t, t->d_interval, 1, idx));
-  TR_TRY(compact_array(t, t->d_status, 1, idx));
-  TR_TRY(compact_array(t, t->d_steps, 1, idx));
-  TR_TRY(compact_array(t, t->d_type, 1, idx));
+  HS_TRY(compact_array(t, t->d_host, 1, idx));
+  HS_TRY(compact_array(t, t->d_u, 1, idx));
+  HS_TRY(compact_array(t, t->d_v, 1, idx));
+  HS_TRY(compact_array(t, t->d_color, 8, idx));
+  HS_TRY(compact_array(t, t->d_weights, 8, idx));
+  HS_TRY(compact_array(t, t->d_gradH, 4, idx));
+  HS_TRY(compact_array(t, t->d_energyTH, 1, idx));
+  HS_TRY(compact_array(t, t->d_quality, 1, idx));
+  HS_TRY(compact_array(t, t->d_idmin, 1, idx));
+  HS_TRY(compact_array(t, t->d_idmax, 1, idx));
+  HS_TRY(compact_array(t, t->d_uv, 2, idx));
+  HS_TRY(compact_array(t, t->d_interval, 1, idx));
+  HS_TRY(compact_array(t, t->d_status, 1, idx));
+  HS_TRY(compact_array(t, t->d_steps, 1, idx));
+  HS_TRY(compact_array(t, t->d_type, 1, idx));
   std::vector<int> hosts(idx.size());
-  if (!idx.empty()) TR_HIP(hipMemcpy(hosts.data(), t->d_host, sizeof(int) * idx.size(), hipMemcpyDeviceToHost));
+  if (!idx.empty()) HS_HIP(hipMemcpy(hosts.data(), t->d_host, sizeof(int) * idx.size(), hipMemcpyDeviceToHost));
   t->max_host = -1;
   for (int h : hosts) t->max_host = std::max(t->max_host, h);
   t->n = (int)idx.size();

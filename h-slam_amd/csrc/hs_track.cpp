@@ -18,24 +18,6 @@
 #include "../../include/hs_undist.h"
 #include "hs_undist_kernels.h"
 
-namespace {
-int tfail(int code, const std::string& msg) {
-  hs::g_err = msg;
-  return code;
-}
-}  // namespace
-
-#define TS_HIP(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) return tfail(HS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define TS_TRY(x)        \
-  do {                   \
-    int rc_ = (x);       \
-    if (rc_) return rc_; \
-  } while (0)
-
 // a captured makeCoarseDepthL0 (make_depth_l0 from a device count): ~32 launches and copies, replayed as one graph;
 // keyed by everything its launches bake in (the reference pyramid's level pointers swap on a promoted frame)
 struct DepthGraph {
@@ -46,13 +28,11 @@ struct DepthGraph {
   hipGraphExec_t exec = nullptr;
 };
 
-struct hs_tracker {
+struct hs_tracker : hs::Device {  // e0, e1: the per-call event pair (hs_tracker_set_event_timing, off by default)
   hs_params P;
-  int device = 0;
+  hs::Pool pool;
   DepthGraph dg[2];
   int dg_next = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;  // the per-call event pair (hs_tracker_set_event_timing, off by default)
   hipEvent_t ev_handoff = nullptr;        // cross-stream hand-offs with a BA context (set_ref_ba, frame_to_ba)
   int evt = 0;                            // hs_tracker_set_event_timing
   int W = 0, H = 0, nlev = 0;
@@ -101,10 +81,10 @@ static int upload_pyr(hs_tracker* t, float4** dst, const float* const* pyr) {
     const size_t n = (size_t)t->w[l] * t->h[l];
     std::vector<float4> tex(n);
     const float* s = pyr[l];
-    if (!s) return tfail(HS_ERR_INVALID, "null pyramid level");
-    for (size_t i = 0; i < n; i++) tex[i] = make_float4(s[3 * i], s[3 * i + 1], s[3 * i + 2], 0.f);
-    TS_HIP(hipMemcpyAsync(dst[l], tex.data(), n * sizeof(float4), hipMemcpyHostToDevice, t->stream));
-    TS_HIP(hipStreamSynchronize(t->stream));  // tex is a temporary
+    if (!s) return hs::fail(HS_ERR_INVALID, "null pyramid level");
+    hs::texels_from_triplets(tex.data(), s, n);
+    HS_HIP(hipMemcpyAsync(dst[l], tex.data(), n * sizeof(float4), hipMemcpyHostToDevice, t->stream));
+    HS_HIP(hipStreamSynchronize(t->stream));  // tex is a temporary
   }
   return HS_OK;
 }
@@ -120,31 +100,26 @@ static size_t done_bytes(int n) { return cnt_bytes(n); }  // the pinned done wor
 
 static int ensure_tries(hs_tracker* t, int n) {
   if (n <= t->try_cap) return HS_OK;
-  if (t->d_Tin) (void)hipFree(t->d_Tin);
-  if (t->d_cnt) (void)hipFree(t->d_cnt);
-  if (t->h_cnt) (void)hipHostFree(t->h_cnt);
-  if (t->d_lmlog) (void)hipFree(t->d_lmlog);
-  if (t->d_part) (void)hipFree(t->d_part);
-  if (t->h_in) (void)hipHostFree(t->h_in);
-  t->d_part = nullptr; t->d_cnt = nullptr; t->h_in = nullptr; t->h_cnt = nullptr;
-  if (t->d_lmlvl) (void)hipFree(t->d_lmlvl);
-  t->d_Tin = nullptr; t->d_out = nullptr; t->h_out = nullptr; t->d_lmlog = nullptr; t->d_lmlvl = nullptr;
-  TS_HIP(hipMalloc((void**)&t->d_Tin, sizeof(double) * 9 * n));  // T (7) | aff (2)
-  TS_HIP(hipMalloc((void**)&t->d_cnt, cnt_bytes(n) + sizeof(HsTryOut) * n));
+  hs::Pool& m = t->pool;  // the pool owns d_cnt and h_cnt; d_out, h_out, h_done and the dh_* views point into them
+  t->try_cap = 0;
+  t->d_out = nullptr;
+  t->h_out = nullptr;
+  HS_TRY(m.alloc(&t->d_Tin, 9 * (size_t)n));  // T (7) | aff (2)
+  HS_TRY(m.alloc(&t->d_cnt, (cnt_bytes(n) + sizeof(HsTryOut) * n) / sizeof(unsigned int)));
   t->d_out = reinterpret_cast<HsTryOut*>(reinterpret_cast<char*>(t->d_cnt) + cnt_bytes(n));
-  TS_HIP(hipMalloc((void**)&t->d_lmlog, sizeof(double) * 3 * HS_TRK_MAXLOG * n));
-  TS_HIP(hipMalloc((void**)&t->d_lmlvl, sizeof(int) * HS_TRK_MAXLOG * n));
-  TS_HIP(hipMalloc((void**)&t->d_part, part_bytes(n)));
+  HS_TRY(m.alloc(&t->d_lmlog, 3 * (size_t)HS_TRK_MAXLOG * n));
+  HS_TRY(m.alloc(&t->d_lmlvl, (size_t)HS_TRK_MAXLOG * n));
+  HS_TRY(m.alloc(&t->d_part, part_bytes(n) / sizeof(double)));
   // mapped, coherent: the kernel may write the flags and records straight into it (HS_TRK_ZC, run_tries)
-  TS_HIP(hipHostMalloc((void**)&t->h_cnt, cnt_bytes(n) + sizeof(HsTryOut) * n + done_bytes(n),
-                       hipHostMallocMapped | hipHostMallocCoherent));
+  HS_TRY(m.pinned(&t->h_cnt, (cnt_bytes(n) + sizeof(HsTryOut) * n + done_bytes(n)) / sizeof(unsigned int),
+                  hipHostMallocMapped | hipHostMallocCoherent));
   t->h_out = reinterpret_cast<HsTryOut*>(reinterpret_cast<char*>(t->h_cnt) + cnt_bytes(n));
   t->h_done = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(t->h_out) + sizeof(HsTryOut) * n);
   std::memset(t->h_cnt, 0, cnt_bytes(n) + sizeof(HsTryOut) * n + done_bytes(n));
-  TS_HIP(hipHostGetDevicePointer((void**)&t->dh_cnt, t->h_cnt, 0));
+  HS_HIP(hipHostGetDevicePointer((void**)&t->dh_cnt, t->h_cnt, 0));
   t->dh_out = reinterpret_cast<HsTryOut*>(reinterpret_cast<char*>(t->dh_cnt) + cnt_bytes(n));
   t->dh_done = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(t->dh_out) + sizeof(HsTryOut) * n);
-  TS_HIP(hipHostMalloc((void**)&t->h_in, sizeof(double) * 9 * n));
+  HS_TRY(m.pinned(&t->h_in, 9 * (size_t)n));
   t->try_cap = n;
   t->epoch = 0;  // fresh granules and flags: zeroed at the next member-meeting launch
   return HS_OK;
@@ -177,7 +152,7 @@ static HsTrackArgs make_args(hs_tracker* t) {
 // (the rerun after a G-member meeting timed out)
 static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int single_pass, int lvl, float cutoff,
                      bool force_g1 = false) {
-  TS_TRY(ensure_tries(t, n));
+  HS_TRY(ensure_tries(t, n));
   HsTrackArgs a = make_args(t);
   a.n_inl = 0;
   if (n <= HS_TRK_INL) {  // a few hypotheses travel in the kernel arguments: no upload
@@ -185,7 +160,7 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
     std::memcpy(a.inl, h_in, sizeof(double) * 9 * n);
   } else {
     std::memcpy(t->h_in, h_in, sizeof(double) * 9 * n);
-    TS_HIP(hipMemcpyAsync(t->d_Tin, t->h_in, sizeof(double) * 9 * n, hipMemcpyHostToDevice, t->stream));
+    HS_HIP(hipMemcpyAsync(t->d_Tin, t->h_in, sizeof(double) * 9 * n, hipMemcpyHostToDevice, t->stream));
   }
   a.coarsest = coarsest;
   a.T_in = t->d_Tin;
@@ -238,8 +213,8 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   // epoch starts over (a fresh allocation, or 2^20 - 1 launches)
   if (G > 1) {
     if (t->epoch == 0 || t->epoch >= (1u << (32 - HS_TRK_PASS_BITS)) - 1) {
-      TS_HIP(hipMemsetAsync(t->d_part, 0, part_bytes(t->try_cap), t->stream));
-      TS_HIP(hipMemsetAsync(t->d_cnt, 0, sizeof(unsigned int) * t->try_cap, t->stream));
+      HS_HIP(hipMemsetAsync(t->d_part, 0, part_bytes(t->try_cap), t->stream));
+      HS_HIP(hipMemsetAsync(t->d_cnt, 0, sizeof(unsigned int) * t->try_cap, t->stream));
       std::memset(t->h_cnt, 0, sizeof(unsigned int) * t->try_cap);  // (no launch in flight: every call waits)
       t->epoch = 0;
     }
@@ -252,12 +227,10 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   if (kt && kt[0] == '1' && !single_pass) {
     const int nb = nblk;
     if (nb > t->trace_cap) {  // grown once to the largest block count (freed by hs_tracker_destroy)
-      if (t->d_trace) (void)hipFree(t->d_trace);
-      t->d_trace = nullptr;
-      TS_HIP(hipMalloc((void**)&t->d_trace, sizeof(long long) * 16 * nb));
+      HS_TRY(t->pool.alloc(&t->d_trace, 16 * (size_t)nb));
       t->trace_cap = nb;
     }
-    TS_HIP(hipMemsetAsync(t->d_trace, 0, sizeof(long long) * 16 * nb, t->stream));
+    HS_HIP(hipMemsetAsync(t->d_trace, 0, sizeof(long long) * 16 * nb, t->stream));
     a.trace = t->d_trace;
   }
   // the launch's device time (hs_tracker_last_ms) from an event pair around it, only with event timing on
@@ -265,12 +238,12 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   // from the hypotheses' done words and last_ms stays 0.  Env HS_TRK_NOEVT=0 / 1 (read per call) forces either.
   const char* ne = std::getenv("HS_TRK_NOEVT");
   const bool no_evt = ne ? ne[0] == '1' : !t->evt;
-  if (!no_evt) TS_HIP(hipEventRecord(t->e0, t->stream));
+  if (!no_evt) HS_HIP(hipEventRecord(t->e0, t->stream));
   hipLaunchKernelGGL(hs_k_track, dim3(nblk), dim3(512), 0, t->stream, a);
-  TS_HIP(hipGetLastError());
-  if (!no_evt) TS_HIP(hipEventRecord(t->e1, t->stream));
+  HS_HIP(hipGetLastError());
+  if (!no_evt) HS_HIP(hipEventRecord(t->e1, t->stream));
   if (!zc)  // the timeout flags and the outputs of the n hypotheses, in one read-back
-    TS_HIP(hipMemcpyAsync(t->h_cnt, t->d_cnt, cnt_bytes(t->try_cap) + sizeof(HsTryOut) * n, hipMemcpyDeviceToHost,
+    HS_HIP(hipMemcpyAsync(t->h_cnt, t->d_cnt, cnt_bytes(t->try_cap) + sizeof(HsTryOut) * n, hipMemcpyDeviceToHost,
                           t->stream));
   // zero-copy without the event pair or a trace: wait for every hypothesis' done word (its record and flags are in
   // place before it) instead of the launch's end; bounded, then the synchronize as before.  Otherwise the synchronize.
@@ -287,22 +260,22 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
       if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) break;
     }
   }
-  if (!waited) TS_HIP(hipStreamSynchronize(t->stream));  // (zero-copy: the records are in place once the launch completed)
+  if (!waited) HS_HIP(hipStreamSynchronize(t->stream));  // (zero-copy: the records are in place once the launch completed)
   for (int i = 0; G > 1 && i < n; i++)
     if (t->h_cnt[i] == t->epoch) {  // a meeting timed out: the launch's results are void, rerun every hypothesis with G = 1
       t->fallbacks++;
       return run_tries(t, n, h_in, coarsest, single_pass, lvl, cutoff, true);
     }
   float ms = 0;
-  if (!no_evt) TS_HIP(hipEventElapsedTime(&ms, t->e0, t->e1));
+  if (!no_evt) HS_HIP(hipEventElapsedTime(&ms, t->e0, t->e1));
   t->last_ms = ms;
   t->last_n_tries = single_pass ? 0 : n;
   if (a.trace) {
     long long h[16];
-    TS_HIP(hipMemcpy(h, t->d_trace, sizeof(h), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(h, t->d_trace, sizeof(h), hipMemcpyDeviceToHost));
     {  // placement probe: block -> xcd / cu (h, g)
       std::vector<long long> pl((size_t)nblk * 16);
-      TS_HIP(hipMemcpy(pl.data(), t->d_trace, sizeof(long long) * pl.size(), hipMemcpyDeviceToHost));
+      HS_HIP(hipMemcpy(pl.data(), t->d_trace, sizeof(long long) * pl.size(), hipMemcpyDeviceToHost));
       std::fprintf(stderr, "[trk place]");
       for (int b = 0; b < nblk && b < 64; b++) {
         const long long v = pl[(size_t)b * 16 + 14];
@@ -338,26 +311,26 @@ static bool replay_abort(const HsTryOut& o, const double minRes[5], double lastR
 // weight maps in point order, summed up the pyramid, dilated, normalised and compacted into the pc_* arrays.
 static int make_depth_l0(hs_tracker* t, int n_host, const int* d_n, const float* pts, int stride) {
   const size_t n0 = (size_t)t->w[0] * t->h[0];
-  TS_HIP(hipMemsetAsync(t->d_id[0], 0, n0 * sizeof(float), t->stream));
-  TS_HIP(hipMemsetAsync(t->d_ws[0], 0, n0 * sizeof(float), t->stream));
+  HS_HIP(hipMemsetAsync(t->d_id[0], 0, n0 * sizeof(float), t->stream));
+  HS_HIP(hipMemsetAsync(t->d_ws[0], 0, n0 * sizeof(float), t->stream));
   if (d_n || n_host > 0)
     hipLaunchKernelGGL(hs_k_trk_scatter_sorted, dim3(1), dim3(1024), sizeof(unsigned long long) * HS_TRK_SCAT_CAP,
                        t->stream, d_n, n_host, pts, pts + stride, pts + 2 * (size_t)stride, pts + 3 * (size_t)stride,
                        t->w[0], t->h[0], t->d_id[0], t->d_ws[0]);
-  TS_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   for (int l = 1; l < t->nlev; l++) {
     const int np = t->w[l] * t->h[l];
     hipLaunchKernelGGL(hs_k_trk_down, dim3((np + 255) / 256), dim3(256), 0, t->stream, t->w[l], t->h[l], t->w[l - 1],
                        t->d_id[l - 1], t->d_ws[l - 1], t->d_id[l], t->d_ws[l]);
-    TS_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
   for (int l = 0; l < t->nlev; l++) {
     const int np = t->w[l] * t->h[l];
-    TS_HIP(hipMemcpyAsync(t->d_bak[l], t->d_ws[l], np * sizeof(float), hipMemcpyDeviceToDevice, t->stream));
+    HS_HIP(hipMemcpyAsync(t->d_bak[l], t->d_ws[l], np * sizeof(float), hipMemcpyDeviceToDevice, t->stream));
     const int inner = np - 2 * t->w[l];
     hipLaunchKernelGGL(hs_k_trk_dilate, dim3((inner + 255) / 256), dim3(256), 0, t->stream, t->w[l], t->h[l],
                        l < 2 ? 1 : 0, t->d_bak[l], t->d_id[l], t->d_ws[l]);
-    TS_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
   for (int l = 0; l < t->nlev; l++) {
     const int np = t->w[l] * t->h[l], nb = (np + 255) / 256;
@@ -366,7 +339,7 @@ static int make_depth_l0(hs_tracker* t, int n_host, const int* d_n, const float*
     hipLaunchKernelGGL(hs_k_trk_scan, dim3(1), dim3(1024), 0, t->stream, nb, t->d_bcnt, t->d_boff, t->d_pcn + l);
     hipLaunchKernelGGL(hs_k_trk_compact, dim3(nb), dim3(256), 0, t->stream, t->w[l], t->h[l], t->d_id[l], t->d_ws[l],
                        t->d_ref[l], t->d_boff, t->d_pu[l], t->d_pv[l], t->d_pid[l], t->d_pcol[l]);
-    TS_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
   }
   return HS_OK;
 }
@@ -388,7 +361,7 @@ static int make_depth_l0_dev(hs_tracker* t, const int* d_n, const float* pts, in
     t->dg_next ^= 1;
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
     g.exec = nullptr;
-    TS_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
+    HS_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
     const int rc = make_depth_l0(t, 0, d_n, pts, stride);
     hipGraph_t graph = nullptr;
     const hipError_t ec = hipStreamEndCapture(t->stream, &graph);
@@ -396,12 +369,12 @@ static int make_depth_l0_dev(hs_tracker* t, const int* d_n, const float* pts, in
       if (graph) (void)hipGraphDestroy(graph);
       return rc;
     }
-    if (ec != hipSuccess) return tfail(HS_ERR_HIP, "makeCoarseDepthL0 capture failed");
+    if (ec != hipSuccess) return hs::fail(HS_ERR_HIP, "makeCoarseDepthL0 capture failed");
     const hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (ei != hipSuccess) {
       g.exec = nullptr;
-      return tfail(HS_ERR_HIP, "makeCoarseDepthL0 graph instantiation failed");
+      return hs::fail(HS_ERR_HIP, "makeCoarseDepthL0 graph instantiation failed");
     }
     g.d_n = d_n;
     g.pts = pts;
@@ -409,7 +382,7 @@ static int make_depth_l0_dev(hs_tracker* t, const int* d_n, const float* pts, in
     for (int l = 0; l < HS_TRK_MAXLEV; l++) g.ref[l] = l < t->nlev ? t->d_ref[l] : nullptr;
     hit = &g;
   }
-  TS_HIP(hipGraphLaunch(hit->exec, t->stream));
+  HS_HIP(hipGraphLaunch(hit->exec, t->stream));
   return HS_OK;
 }
 
@@ -417,18 +390,15 @@ extern "C" {
 
 int hs_tracker_create(hs_tracker** out, const hs_params* params, int device_id, int width, int height,
                       int n_levels, const float K4[4]) {
-  if (!out || !K4) return tfail(HS_ERR_INVALID, "null argument");
+  if (!out || !K4) return hs::fail(HS_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (n_levels < 1 || n_levels > HS_TRK_MAXLEV) return tfail(HS_ERR_INVALID, "n_levels out of range");
+  if (n_levels < 1 || n_levels > HS_TRK_MAXLEV) return hs::fail(HS_ERR_INVALID, "n_levels out of range");
   if (width < 16 || height < 16 || (width >> (n_levels - 1)) < 8 || (height >> (n_levels - 1)) < 8)
-    return tfail(HS_ERR_INVALID, "image too small for the pyramid");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return tfail(HS_ERR_HIP, "no HIP device");
-  if (device_id < 0 || device_id >= ndev) return tfail(HS_ERR_INVALID, "bad device id");
+    return hs::fail(HS_ERR_INVALID, "image too small for the pyramid");
+  HS_TRY(hs::check_device(device_id));
   hs_tracker* t = new hs_tracker();
   if (params) t->P = *params;
   else hs_params_default(&t->P);
-  t->device = device_id;
   t->W = width; t->H = height; t->nlev = n_levels;
   // CoarseTracker::makeK (Src/CoarseTracker.cpp:73-101)
   t->w[0] = width; t->h[0] = height;
@@ -445,36 +415,29 @@ int hs_tracker_create(hs_tracker** out, const hs_params* params, int device_id, 
     const float K[9] = {t->fx[l], 0, t->cx[l], 0, t->fy[l], t->cy[l], 0, 0, 1};
     hs::inv3f(K, t->Ki[l]);
   }
-  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreate(&t->e0) != hipSuccess || hipEventCreate(&t->e1) != hipSuccess ||
-      hipEventCreateWithFlags(&t->ev_handoff, hipEventDisableTiming) != hipSuccess) {
-    delete t;
-    return tfail(HS_ERR_HIP, "stream / event creation failed");
-  }
-  if (hipDeviceGetAttribute(&t->n_cu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || t->n_cu < 1)
-    t->n_cu = 1;
-  if (hipDeviceGetAttribute(&t->wclk_khz, hipDeviceAttributeWallClockRate, device_id) != hipSuccess || t->wclk_khz < 1)
-    t->wclk_khz = 100000;
-  int maxBlocks = 1;
-  for (int l = 0; l < n_levels; l++) {
-    const size_t n = (size_t)t->w[l] * t->h[l];
-    TS_HIP(hipMalloc((void**)&t->d_ref[l], n * sizeof(float4)));
-    TS_HIP(hipMalloc((void**)&t->d_new[l], n * sizeof(float4)));
-    TS_HIP(hipMalloc((void**)&t->d_id[l], n * sizeof(float)));
-    TS_HIP(hipMalloc((void**)&t->d_ws[l], n * sizeof(float)));
-    TS_HIP(hipMalloc((void**)&t->d_bak[l], n * sizeof(float)));
-    TS_HIP(hipMalloc((void**)&t->d_pu[l], n * sizeof(float)));
-    TS_HIP(hipMalloc((void**)&t->d_pv[l], n * sizeof(float)));
-    TS_HIP(hipMalloc((void**)&t->d_pid[l], n * sizeof(float)));
-    TS_HIP(hipMalloc((void**)&t->d_pcol[l], n * sizeof(float)));
-    maxBlocks = std::max(maxBlocks, (int)((n + 255) / 256));
-  }
-  TS_HIP(hipMalloc((void**)&t->d_pcn, sizeof(int) * HS_TRK_MAXLEV));
-  TS_HIP(hipMemsetAsync(t->d_pcn, 0, sizeof(int) * HS_TRK_MAXLEV, t->stream));  // on the kernels' stream
-  TS_HIP(hipMalloc((void**)&t->d_bcnt, sizeof(int) * maxBlocks));
-  TS_HIP(hipMalloc((void**)&t->d_boff, sizeof(int) * maxBlocks));
-  *out = t;
-  return HS_OK;
+  const int rc = [&]() -> int {
+    hs::Pool& m = t->pool;
+    HS_TRY(t->open(device_id));
+    HS_HIP(hipEventCreateWithFlags(&t->ev_handoff, hipEventDisableTiming));
+    if (hipDeviceGetAttribute(&t->n_cu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || t->n_cu < 1)
+      t->n_cu = 1;
+    if (hipDeviceGetAttribute(&t->wclk_khz, hipDeviceAttributeWallClockRate, device_id) != hipSuccess || t->wclk_khz < 1)
+      t->wclk_khz = 100000;
+    int maxBlocks = 1;
+    for (int l = 0; l < n_levels; l++) {
+      const size_t n = (size_t)t->w[l] * t->h[l];
+      for (auto* lv : {t->d_ref, t->d_new}) HS_TRY(m.alloc(&lv[l], n));
+      for (auto* lv : {t->d_id, t->d_ws, t->d_bak, t->d_pu, t->d_pv, t->d_pid, t->d_pcol}) HS_TRY(m.alloc(&lv[l], n));
+      maxBlocks = std::max(maxBlocks, (int)((n + 255) / 256));
+    }
+    HS_TRY(m.alloc_zero(&t->d_pcn, HS_TRK_MAXLEV, t->stream));  // on the kernels' stream
+    HS_TRY(m.alloc(&t->d_bcnt, maxBlocks));
+    HS_TRY(m.alloc(&t->d_boff, maxBlocks));
+    return HS_OK;
+  }();
+  if (rc) hs_tracker_destroy(t);
+  else *out = t;
+  return rc;
 }
 
 void hs_tracker_destroy(hs_tracker* t) {
@@ -483,38 +446,24 @@ void hs_tracker_destroy(hs_tracker* t) {
   if (t->stream) (void)hipStreamSynchronize(t->stream);
   for (auto& g : t->dg)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  for (int l = 0; l < HS_TRK_MAXLEV; l++) {
-    void* ps[] = {t->d_ref[l], t->d_new[l], t->d_id[l], t->d_ws[l], t->d_bak[l], t->d_pu[l], t->d_pv[l], t->d_pid[l],
-                  t->d_pcol[l]};
-    for (void* p : ps)
-      if (p) (void)hipFree(p);
-  }
-  void* ps[] = {t->d_pcn, t->d_bcnt, t->d_boff, t->d_pts, t->d_Tin, t->d_cnt, t->d_lmlog, t->d_lmlvl, t->d_raw,
-                t->d_trace, t->d_part};  // d_out lives in d_cnt's allocation, h_out in h_cnt's
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  if (t->h_in) (void)hipHostFree(t->h_in);
-  if (t->h_cnt) (void)hipHostFree(t->h_cnt);
-  if (t->e0) (void)hipEventDestroy(t->e0);
-  if (t->e1) (void)hipEventDestroy(t->e1);
+  t->pool.release_all();
   if (t->ev_handoff) (void)hipEventDestroy(t->ev_handoff);
-  if (t->stream) (void)hipStreamDestroy(t->stream);
+  t->close();
   delete t;
 }
 
 int hs_tracker_set_ref(hs_tracker* t, const float* const* ref_pyr, float ab_exposure, const double aff_g2l[2], int n,
                        const float* cu, const float* cv, const float* cid, const float* hdi) {
   if (!t || !ref_pyr || !aff_g2l || n < 0 || (n > 0 && (!cu || !cv || !cid || !hdi)))
-    return tfail(HS_ERR_INVALID, "null argument");
-  TS_HIP(hipSetDevice(t->device));
-  TS_TRY(upload_pyr(t, t->d_ref, ref_pyr));
+    return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(upload_pyr(t, t->d_ref, ref_pyr));
   t->refExposure = ab_exposure;
   t->refAff[0] = aff_g2l[0];
   t->refAff[1] = aff_g2l[1];
   if (n > t->pts_cap) {
-    if (t->d_pts) (void)hipFree(t->d_pts);
-    t->d_pts = nullptr;
-    TS_HIP(hipMalloc((void**)&t->d_pts, sizeof(float) * 4 * n));
+    t->pts_cap = 0;
+    HS_TRY(t->pool.alloc(&t->d_pts, 4 * (size_t)n));
     t->pts_cap = n;
   }
   std::vector<float> h((size_t)4 * std::max(n, 0));  // lives until the stream synchronize below
@@ -523,18 +472,18 @@ int hs_tracker_set_ref(hs_tracker* t, const float* const* ref_pyr, float ab_expo
     std::memcpy(h.data() + n, cv, 4 * n);
     std::memcpy(h.data() + 2 * n, cid, 4 * n);
     std::memcpy(h.data() + 3 * n, hdi, 4 * n);
-    TS_HIP(hipMemcpyAsync(t->d_pts, h.data(), sizeof(float) * 4 * n, hipMemcpyHostToDevice, t->stream));
+    HS_HIP(hipMemcpyAsync(t->d_pts, h.data(), sizeof(float) * 4 * n, hipMemcpyHostToDevice, t->stream));
   }
-  TS_TRY(make_depth_l0(t, n, nullptr, t->d_pts, n));
-  TS_HIP(hipStreamSynchronize(t->stream));
+  HS_TRY(make_depth_l0(t, n, nullptr, t->d_pts, n));
+  HS_HIP(hipStreamSynchronize(t->stream));
   t->haveRef = true;
   return HS_OK;
 }
 
 int hs_tracker_frame_texels(hs_tracker* t, int lvl, const void** d_texels) {
-  if (!t || !d_texels) return tfail(HS_ERR_INVALID, "null argument");
-  if (lvl < 0 || lvl >= t->nlev) return tfail(HS_ERR_INVALID, "bad level");
-  if (!t->haveFrame) return tfail(HS_ERR_STATE, "no frame set");
+  if (!t || !d_texels) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (lvl < 0 || lvl >= t->nlev) return hs::fail(HS_ERR_INVALID, "bad level");
+  if (!t->haveFrame) return hs::fail(HS_ERR_STATE, "no frame set");
   *d_texels = t->d_new[lvl];
   return HS_OK;
 }
@@ -543,35 +492,35 @@ int hs_tracker_frame_texels(hs_tracker* t, int lvl, const void** d_texels) {
 // on the device: the points whose residual into the newest frame is IN, in window order (hs_k_win_newest on the BA
 // stream), then makeCoarseDepthL0 on the tracker stream after an event -- no host round trip, no host sync.
 int hs_tracker_set_ref_ba(hs_tracker* t, hs_ctx* ba, int promote_frame, float ab_exposure, const double aff_g2l[2]) {
-  if (!t || !ba || !aff_g2l) return tfail(HS_ERR_INVALID, "null argument");
-  if (ba->device != t->device) return tfail(HS_ERR_INVALID, "tracker and BA context on different devices");
-  TS_HIP(hipSetDevice(t->device));
+  if (!t || !ba || !aff_g2l) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (ba->device != t->device) return hs::fail(HS_ERR_INVALID, "tracker and BA context on different devices");
+  HS_HIP(hipSetDevice(t->device));
   HS_TRY(hs::commit_if_dirty(ba));
-  if (ba->nF < 1) return tfail(HS_ERR_STATE, "empty BA window");
-  if (ba->cam.width != t->W || ba->cam.height != t->H) return tfail(HS_ERR_INVALID, "image size mismatch");
-  if (promote_frame && !t->haveFrame) return tfail(HS_ERR_STATE, "no frame to promote");
+  if (ba->nF < 1) return hs::fail(HS_ERR_STATE, "empty BA window");
+  if (ba->cam.width != t->W || ba->cam.height != t->H) return hs::fail(HS_ERR_INVALID, "image size mismatch");
+  if (promote_frame && !t->haveFrame) return hs::fail(HS_ERR_STATE, "no frame to promote");
   // the hand-off buffer: points of the BA window (capacity), compacted on the BA's stream
   hipLaunchKernelGGL(hs_k_win_newest, dim3(1), dim3(1024), 0, ba->stream, ba->nP, ba->nF - 1, ba->d_res_of_slot,
                      ba->d_r_state, ba->d_r_center, ba->hdif_solved, ba->d_ref_pts, ba->cap_P, ba->d_ref_n);
-  TS_HIP(hipGetLastError());
+  HS_HIP(hipGetLastError());
   if (!promote_frame)  // the reference pyramid's level 0 is the BA's newest frame image
-    TS_HIP(hipMemcpyAsync(t->d_ref[0], ba->d_img_all + (size_t)ba->img_slot[ba->nF - 1] * ba->img_px,
+    HS_HIP(hipMemcpyAsync(t->d_ref[0], ba->d_img_all + (size_t)ba->img_slot[ba->nF - 1] * ba->img_px,
                           sizeof(float4) * (size_t)t->W * t->H, hipMemcpyDeviceToDevice, ba->stream));
-  TS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
-  TS_HIP(hipStreamWaitEvent(t->stream, ba->ev_ready, 0));
+  HS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
+  HS_HIP(hipStreamWaitEvent(t->stream, ba->ev_ready, 0));
   if (promote_frame) {
     for (int l = 0; l < t->nlev; l++) std::swap(t->d_ref[l], t->d_new[l]);
     t->haveFrame = false;  // d_new now holds the old reference: the next frame to track must be set
   } else {
-    TS_HIP(hs_build_dir_pyramid_upper(t->stream, t->W, t->H, t->nlev, t->d_ref));
+    HS_HIP(hs_build_dir_pyramid_upper(t->stream, t->W, t->H, t->nlev, t->d_ref));
   }
   t->refExposure = ab_exposure;
   t->refAff[0] = aff_g2l[0];
   t->refAff[1] = aff_g2l[1];
-  TS_TRY(make_depth_l0_dev(t, ba->d_ref_n, ba->d_ref_pts, ba->cap_P));
+  HS_TRY(make_depth_l0_dev(t, ba->d_ref_n, ba->d_ref_pts, ba->cap_P));
   // the BA stream must not rewrite the hand-off buffer before the tracker consumed it
-  TS_HIP(hipEventRecord(t->ev_handoff, t->stream));
-  TS_HIP(hipStreamWaitEvent(ba->stream, t->ev_handoff, 0));
+  HS_HIP(hipEventRecord(t->ev_handoff, t->stream));
+  HS_HIP(hipStreamWaitEvent(ba->stream, t->ev_handoff, 0));
   t->haveRef = true;
   return HS_OK;
 }
@@ -581,72 +530,72 @@ int hs_tracker_set_ref_ba(hs_tracker* t, hs_ctx* ba, int promote_frame, float ab
 // stream waits for the tracker's stream (the frame's pyramid), the copy and the packed slot run on the BA stream,
 // and the tracker's stream waits for the copy, so its next set_frame cannot rewrite d_new before the copy read it.
 int hs_tracker_frame_to_ba(hs_tracker* t, hs_ctx* ba, int frame) {
-  if (!t || !ba) return tfail(HS_ERR_INVALID, "null argument");
-  if (ba->device != t->device) return tfail(HS_ERR_INVALID, "tracker and BA context on different devices");
-  if (ba->cam.width != t->W || ba->cam.height != t->H) return tfail(HS_ERR_INVALID, "image size mismatch");
-  if (!t->haveFrame) return tfail(HS_ERR_STATE, "no frame set");
-  TS_HIP(hipSetDevice(t->device));
-  TS_HIP(hipEventRecord(t->ev_handoff, t->stream));
-  TS_HIP(hipStreamWaitEvent(ba->stream, t->ev_handoff, 0));
+  if (!t || !ba) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (ba->device != t->device) return hs::fail(HS_ERR_INVALID, "tracker and BA context on different devices");
+  if (ba->cam.width != t->W || ba->cam.height != t->H) return hs::fail(HS_ERR_INVALID, "image size mismatch");
+  if (!t->haveFrame) return hs::fail(HS_ERR_STATE, "no frame set");
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipEventRecord(t->ev_handoff, t->stream));
+  HS_HIP(hipStreamWaitEvent(ba->stream, t->ev_handoff, 0));
   if (const int rc = hs::copy_frame_image_device(ba, frame, t->d_new[0]))
-    return tfail(rc, std::string("hs_tracker_frame_to_ba: ") + hs::g_err);
-  TS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
-  TS_HIP(hipStreamWaitEvent(t->stream, ba->ev_ready, 0));
+    return hs::fail(rc, std::string("hs_tracker_frame_to_ba: ") + hs::g_err);
+  HS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
+  HS_HIP(hipStreamWaitEvent(t->stream, ba->ev_ready, 0));
   return HS_OK;
 }
 
 int hs_tracker_set_event_timing(hs_tracker* t, int on) {
-  if (!t) return tfail(HS_ERR_INVALID, "null tracker");
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracker");
   t->evt = on ? 1 : 0;
   return HS_OK;
 }
 
 int hs_tracker_get_ref(hs_tracker* t, int lvl, int* n, float* u, float* v, float* idepth, float* color) {
-  if (!t || !n) return tfail(HS_ERR_INVALID, "null argument");
-  if (lvl < 0 || lvl >= t->nlev) return tfail(HS_ERR_INVALID, "bad level");
-  if (!t->haveRef) return tfail(HS_ERR_STATE, "no reference set");
-  TS_HIP(hipSetDevice(t->device));
-  TS_HIP(hipStreamSynchronize(t->stream));
-  TS_HIP(hipMemcpy(n, t->d_pcn + lvl, sizeof(int), hipMemcpyDeviceToHost));
+  if (!t || !n) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (lvl < 0 || lvl >= t->nlev) return hs::fail(HS_ERR_INVALID, "bad level");
+  if (!t->haveRef) return hs::fail(HS_ERR_STATE, "no reference set");
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipStreamSynchronize(t->stream));
+  HS_HIP(hipMemcpy(n, t->d_pcn + lvl, sizeof(int), hipMemcpyDeviceToHost));
   const size_t b = sizeof(float) * (size_t)*n;
   if (*n > 0) {
-    if (u) TS_HIP(hipMemcpy(u, t->d_pu[lvl], b, hipMemcpyDeviceToHost));
-    if (v) TS_HIP(hipMemcpy(v, t->d_pv[lvl], b, hipMemcpyDeviceToHost));
-    if (idepth) TS_HIP(hipMemcpy(idepth, t->d_pid[lvl], b, hipMemcpyDeviceToHost));
-    if (color) TS_HIP(hipMemcpy(color, t->d_pcol[lvl], b, hipMemcpyDeviceToHost));
+    if (u) HS_HIP(hipMemcpy(u, t->d_pu[lvl], b, hipMemcpyDeviceToHost));
+    if (v) HS_HIP(hipMemcpy(v, t->d_pv[lvl], b, hipMemcpyDeviceToHost));
+    if (idepth) HS_HIP(hipMemcpy(idepth, t->d_pid[lvl], b, hipMemcpyDeviceToHost));
+    if (color) HS_HIP(hipMemcpy(color, t->d_pcol[lvl], b, hipMemcpyDeviceToHost));
   }
   return HS_OK;
 }
 
 int hs_tracker_set_frame(hs_tracker* t, const float* const* new_pyr, float ab_exposure) {
-  if (!t || !new_pyr) return tfail(HS_ERR_INVALID, "null argument");
-  TS_HIP(hipSetDevice(t->device));
-  TS_TRY(upload_pyr(t, t->d_new, new_pyr));
+  if (!t || !new_pyr) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(upload_pyr(t, t->d_new, new_pyr));
   t->newExposure = ab_exposure;
   t->haveFrame = true;
   return HS_OK;
 }
 
 int hs_tracker_set_frame_raw(hs_tracker* t, const float* img, float ab_exposure) {
-  if (!t || !img) return tfail(HS_ERR_INVALID, "null argument");
-  TS_HIP(hipSetDevice(t->device));
-  if (!t->d_raw) TS_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
-  TS_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
-  TS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
-  TS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
+  if (!t || !img) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_HIP(hipSetDevice(t->device));
+  if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
+  HS_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
+  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
+  HS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
   t->newExposure = ab_exposure;
   t->haveFrame = true;
   return HS_OK;
 }
 
 int hs_tracker_set_frame_u8(hs_tracker* t, hs_undistorter* u, const uint8_t* raw, float ab_exposure) {
-  if (!t || !u || !raw) return tfail(HS_ERR_INVALID, "null argument");
-  TS_TRY(hs_undist_match(u, t->device, t->W, t->H));
-  TS_HIP(hipSetDevice(t->device));
-  if (!t->d_raw) TS_HIP(hipMalloc((void**)&t->d_raw, sizeof(float) * t->W * t->H));
-  TS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
-  TS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
-  TS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
+  if (!t || !u || !raw) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(hs_undist_match(u, t->device, t->W, t->H));
+  HS_HIP(hipSetDevice(t->device));
+  if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
+  HS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
+  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
+  HS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
   t->newExposure = ab_exposure;
   t->haveFrame = true;
   return HS_OK;
@@ -654,15 +603,15 @@ int hs_tracker_set_frame_u8(hs_tracker* t, hs_undistorter* u, const uint8_t* raw
 
 int hs_tracker_calc_res(hs_tracker* t, int lvl, const double T7[7], const double aff[2], float cutoffTH, double res6[6],
                         double H64[64], double b8[8], int* n_warped) {
-  if (!t || !T7 || !aff || !res6) return tfail(HS_ERR_INVALID, "null argument");
-  if (lvl < 0 || lvl >= t->nlev) return tfail(HS_ERR_INVALID, "bad level");
-  if (!t->haveRef || !t->haveFrame) return tfail(HS_ERR_STATE, "reference and frame must be set");
-  TS_HIP(hipSetDevice(t->device));
+  if (!t || !T7 || !aff || !res6) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (lvl < 0 || lvl >= t->nlev) return hs::fail(HS_ERR_INVALID, "bad level");
+  if (!t->haveRef || !t->haveFrame) return hs::fail(HS_ERR_STATE, "reference and frame must be set");
+  HS_HIP(hipSetDevice(t->device));
   double in[9];
   std::memcpy(in, T7, sizeof(double) * 7);
   in[7] = aff[0];
   in[8] = aff[1];
-  TS_TRY(run_tries(t, 1, in, lvl, 1, lvl, cutoffTH));
+  HS_TRY(run_tries(t, 1, in, lvl, 1, lvl, cutoffTH));
   const HsTryOut& o = t->h_out[0];
   std::memcpy(res6, o.res6, sizeof(double) * 6);
   if (H64) std::memcpy(H64, o.H, sizeof(double) * 64);
@@ -674,16 +623,16 @@ int hs_tracker_calc_res(hs_tracker* t, int lvl, const double T7[7], const double
 int hs_tracker_track(hs_tracker* t, double T_inout[7], double aff_inout[2], int coarsest_lvl,
                      const double minResForAbort[5], double lastResiduals[5], double flow[3], int* ok) {
   if (!t || !T_inout || !aff_inout || !minResForAbort || !lastResiduals || !flow || !ok)
-    return tfail(HS_ERR_INVALID, "null argument");
+    return hs::fail(HS_ERR_INVALID, "null argument");
   if (coarsest_lvl < 0 || coarsest_lvl >= t->nlev || coarsest_lvl >= 5)
-    return tfail(HS_ERR_INVALID, "coarsest level must be < min(5, n_levels)");
-  if (!t->haveRef || !t->haveFrame) return tfail(HS_ERR_STATE, "reference and frame must be set");
-  TS_HIP(hipSetDevice(t->device));
+    return hs::fail(HS_ERR_INVALID, "coarsest level must be < min(5, n_levels)");
+  if (!t->haveRef || !t->haveFrame) return hs::fail(HS_ERR_STATE, "reference and frame must be set");
+  HS_HIP(hipSetDevice(t->device));
   double in[9];
   std::memcpy(in, T_inout, sizeof(double) * 7);
   in[7] = aff_inout[0];
   in[8] = aff_inout[1];
-  TS_TRY(run_tries(t, 1, in, coarsest_lvl, 0, 0, 0.f));
+  HS_TRY(run_tries(t, 1, in, coarsest_lvl, 0, 0, 0.f));
   const HsTryOut& o = t->h_out[0];
   const bool good = replay_abort(o, minResForAbort, lastResiduals, flow);
   *ok = good ? 1 : 0;
@@ -703,9 +652,9 @@ int hs_tracker_track_tries(hs_tracker* t, int n_tries, const double* tries7, con
                            double achievedRes[5], double flowVecs[3], int* have_one_good, int* n_tried) {
   if (!t || n_tries < 1 || !tries7 || !aff_last || !lastCoarseRMSE || !T_out || !aff_out || !achievedRes || !flowVecs ||
       !have_one_good || !n_tried)
-    return tfail(HS_ERR_INVALID, "null argument");
-  if (!t->haveRef || !t->haveFrame) return tfail(HS_ERR_STATE, "reference and frame must be set");
-  TS_HIP(hipSetDevice(t->device));
+    return hs::fail(HS_ERR_INVALID, "null argument");
+  if (!t->haveRef || !t->haveFrame) return hs::fail(HS_ERR_STATE, "reference and frame must be set");
+  HS_HIP(hipSetDevice(t->device));
   const int coarsest = std::min(t->nlev - 1, 4);
   std::vector<double> in((size_t)9 * n_tries);
   std::memcpy(in.data(), tries7, sizeof(double) * 7 * n_tries);
@@ -713,7 +662,7 @@ int hs_tracker_track_tries(hs_tracker* t, int n_tries, const double* tries7, con
     in[7 * n_tries + 2 * i] = aff_last[0];
     in[7 * n_tries + 2 * i + 1] = aff_last[1];
   }
-  TS_TRY(run_tries(t, n_tries, in.data(), coarsest, 0, 0, 0.f));
+  HS_TRY(run_tries(t, n_tries, in.data(), coarsest, 0, 0, 0.f));
   // System::trackNewCoarse try loop (Src/System.cpp:413-481), replayed in the reference's order
   double ach[5];
   for (int k = 0; k < 5; k++) ach[k] = NAN;
@@ -754,19 +703,19 @@ int hs_tracker_track_tries(hs_tracker* t, int n_tries, const double* tries7, con
 
 int hs_tracker_get_lm_log(hs_tracker* t, int try_idx, int cap, int* n, int* lvl, double* new_ratio,
                           double* old_ratio, double* inc_norm) {
-  if (!t || !n) return tfail(HS_ERR_INVALID, "null argument");
-  if (try_idx < 0 || try_idx >= t->last_n_tries) return tfail(HS_ERR_INVALID, "no such hypothesis in the last call");
-  TS_HIP(hipSetDevice(t->device));
-  TS_HIP(hipStreamSynchronize(t->stream));
+  if (!t || !n) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (try_idx < 0 || try_idx >= t->last_n_tries) return hs::fail(HS_ERR_INVALID, "no such hypothesis in the last call");
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipStreamSynchronize(t->stream));
   const int iters = t->h_out[try_idx].iters;
   *n = iters;
   const int m = std::min(std::min(iters, cap), HS_TRK_MAXLOG);
   if (m > 0) {
     std::vector<double> lg((size_t)3 * m);
-    TS_HIP(hipMemcpy(lg.data(), t->d_lmlog + (size_t)try_idx * HS_TRK_MAXLOG * 3, sizeof(double) * 3 * m,
+    HS_HIP(hipMemcpy(lg.data(), t->d_lmlog + (size_t)try_idx * HS_TRK_MAXLOG * 3, sizeof(double) * 3 * m,
                      hipMemcpyDeviceToHost));
     if (lvl)
-      TS_HIP(hipMemcpy(lvl, t->d_lmlvl + (size_t)try_idx * HS_TRK_MAXLOG, sizeof(int) * m, hipMemcpyDeviceToHost));
+      HS_HIP(hipMemcpy(lvl, t->d_lmlvl + (size_t)try_idx * HS_TRK_MAXLOG, sizeof(int) * m, hipMemcpyDeviceToHost));
     for (int i = 0; i < m; i++) {
       if (new_ratio) new_ratio[i] = lg[3 * i];
       if (old_ratio) old_ratio[i] = lg[3 * i + 1];
@@ -777,8 +726,8 @@ int hs_tracker_get_lm_log(hs_tracker* t, int try_idx, int cap, int* n, int* lvl,
 }
 
 int hs_tracker_last_stats(hs_tracker* t, int try_idx, double* ms, int* passes, long long* point_passes) {
-  if (!t) return tfail(HS_ERR_INVALID, "null tracker");
-  if (try_idx < 0 || try_idx >= t->last_n_tries) return tfail(HS_ERR_INVALID, "no such hypothesis in the last call");
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracker");
+  if (try_idx < 0 || try_idx >= t->last_n_tries) return hs::fail(HS_ERR_INVALID, "no such hypothesis in the last call");
   if (ms) *ms = t->last_ms;
   if (passes) *passes = t->h_out[try_idx].passes;
   if (point_passes) *point_passes = t->h_out[try_idx].point_passes;
@@ -786,14 +735,14 @@ int hs_tracker_last_stats(hs_tracker* t, int try_idx, double* ms, int* passes, l
 }
 
 int hs_tracker_launch_info(hs_tracker* t, int* G, int* fallbacks) {
-  if (!t) return tfail(HS_ERR_INVALID, "null tracker");
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracker");
   if (G) *G = t->last_G;
   if (fallbacks) *fallbacks = t->fallbacks;
   return HS_OK;
 }
 
 int hs_tracker_last_ms(hs_tracker* t, double* ms) {
-  if (!t || !ms) return tfail(HS_ERR_INVALID, "null argument");
+  if (!t || !ms) return hs::fail(HS_ERR_INVALID, "null argument");
   *ms = t->last_ms;
   return HS_OK;
 }

@@ -13,18 +13,11 @@
 
 #include "../../include/hs_ba.h"
 #include "../../include/hs_undist.h"
+#define HS_HOST_ERRORS_ONLY
+#include "hs_host.h"
 #include "hs_undist_tables.h"
 
-namespace hs {
-extern thread_local std::string g_err;
-}
-
 namespace {
-int ufail(int code, const std::string& msg) {
-  hs::g_err = msg;
-  return code;
-}
-
 struct Cam {
   int model;
   double ic[8];  // input fx fy cx cy, then the distortion parameters
@@ -182,7 +175,7 @@ int optimal_k_crop(Cam& c, int w, int h, int wOrg, int hOrg) {
     if (oobT) minY = (float)((double)minY * 0.995);
     if (oobB) maxY = (float)((double)maxY * 0.995);
     iteration++;
-    if (iteration > 500) return ufail(HS_ERR_INVALID, "crop: no output K found in 500 iterations");
+    if (iteration > 500) return hs::fail(HS_ERR_INVALID, "crop: no output K found in 500 iterations");
   }
   c.K[0] = (double)(((float)w - 1.0f) / (maxX - minX));
   c.K[1] = (double)(((float)h - 1.0f) / (maxY - minY));
@@ -196,23 +189,23 @@ int hs_undist_check_map(const float* remap_x, const float* remap_y, size_t n) {
   for (size_t i = 0; i < n; i++) {
     const float x = remap_x[i], y = remap_y[i];
     if (!(x >= -32767.f && x <= 32767.f && y >= -32767.f && y <= 32767.f))
-      return ufail(HS_ERR_INVALID, "remap value not finite or outside +-32767");
+      return hs::fail(HS_ERR_INVALID, "remap value not finite or outside +-32767");
   }
   return HS_OK;
 }
 
 extern "C" int hs_undist_make_remap(const hs_undist_calib* cal, float K_out[4], float* remap_x, float* remap_y) {
-  if (!cal || !K_out || !remap_x || !remap_y) return ufail(HS_ERR_INVALID, "null argument");
+  if (!cal || !K_out || !remap_x || !remap_y) return hs::fail(HS_ERR_INVALID, "null argument");
   if (cal->model < HS_CAM_PINHOLE || cal->model > HS_CAM_KANNALABRANDT)
-    return ufail(HS_ERR_INVALID, "bad camera model");
-  if (cal->process < HS_UNDIST_CROP || cal->process > HS_UNDIST_USEK) return ufail(HS_ERR_INVALID, "bad process");
+    return hs::fail(HS_ERR_INVALID, "bad camera model");
+  if (cal->process < HS_UNDIST_CROP || cal->process > HS_UNDIST_USEK) return hs::fail(HS_ERR_INVALID, "bad process");
   const int w = cal->w_out, h = cal->h_out, wOrg = cal->w_in, hOrg = cal->h_in;
   if (w <= 0 || h <= 0 || wOrg <= 0 || hOrg <= 0 || (long long)w * h >= (1LL << 30) ||
       (long long)wOrg * hOrg >= (1LL << 30))
-    return ufail(HS_ERR_INVALID, "bad image size");
-  if (cal->process == HS_UNDIST_CROP && (w < 2 || h < 2)) return ufail(HS_ERR_INVALID, "crop needs an output of 2x2 or more");
+    return hs::fail(HS_ERR_INVALID, "bad image size");
+  if (cal->process == HS_UNDIST_CROP && (w < 2 || h < 2)) return hs::fail(HS_ERR_INVALID, "crop needs an output of 2x2 or more");
   if (cal->process == HS_UNDIST_NONE && (w != wOrg || h != hOrg))
-    return ufail(HS_ERR_INVALID, "process none requires equal input and output sizes");
+    return hs::fail(HS_ERR_INVALID, "process none requires equal input and output sizes");
 
   Cam c;
   c.model = cal->model;
@@ -237,7 +230,7 @@ extern "C" int hs_undist_make_remap(const hs_undist_calib* cal, float K_out[4], 
     for (int i = 0; i < 4; i++) c.K[i] = Kl[i];
   } else {
     if (cal->desired_K[2] > 1 || cal->desired_K[3] > 1)
-      return ufail(HS_ERR_INVALID, "desired_K must be relative to the output width and height");
+      return hs::fail(HS_ERR_INVALID, "desired_K must be relative to the output width and height");
     c.K[0] = cal->desired_K[0] * w;
     c.K[1] = cal->desired_K[1] * h;
     c.K[2] = cal->desired_K[2] * w - 0.5;
@@ -277,13 +270,13 @@ extern "C" int hs_undist_make_remap(const hs_undist_calib* cal, float K_out[4], 
 
 extern "C" int hs_undist_make_photometric(const float* G256, const uint16_t* vignette, int n_in, float Binv[256],
                                           float B[256], float* vignette_inv) {
-  if (!Binv || !B) return ufail(HS_ERR_INVALID, "null argument");
-  if (vignette && (!vignette_inv || n_in <= 0)) return ufail(HS_ERR_INVALID, "vignette without an output or a size");
+  if (!Binv || !B) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (vignette && (!vignette_inv || n_in <= 0)) return hs::fail(HS_ERR_INVALID, "vignette without an output or a size");
   if (G256) {
     for (int i = 0; i < 256; i++)
-      if (!std::isfinite(G256[i])) return ufail(HS_ERR_INVALID, "G is not finite");
+      if (!std::isfinite(G256[i])) return hs::fail(HS_ERR_INVALID, "G is not finite");
     for (int i = 0; i < 255; i++)
-      if (G256[i + 1] <= G256[i]) return ufail(HS_ERR_INVALID, "G must have 256 strictly increasing entries");
+      if (G256[i + 1] <= G256[i]) return hs::fail(HS_ERR_INVALID, "G must have 256 strictly increasing entries");
     const float mn = G256[0], mx = G256[255];
     for (int i = 0; i < 256; i++) Binv[i] = (float)(255.0 * (double)(G256[i] - mn) / (double)(mx - mn));
   } else {
