@@ -32,6 +32,7 @@ struct hs_extractor : hs::Device {
   unsigned long long umax = 0;
   float* d_map = nullptr;    // the caller's map (hs_extractor_extract)
   uint8_t* d_img = nullptr;  // cvImgL
+  bool have_img = false;     // an extract has filled d_img (hs_extract_image)
   char4* d_pattern = nullptr;
   int* d_row_cnt = nullptr;
   int* d_count = nullptr;
@@ -125,6 +126,7 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
   HS_HIP(hipEventRecord(e->e1, s));
   HS_HIP(hipMemcpyAsync(e->h_count, e->d_count, sizeof(int), hipMemcpyDeviceToHost, s));
   HS_HIP(hipStreamSynchronize(s));  // the one wait of an extract
+  e->have_img = true;
   HS_HIP(hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
   const int n = *e->h_count;
   if (n_keys) *n_keys = n;
@@ -158,6 +160,15 @@ void hs_extract_keys(hs_extractor* e, int* device, int* W, int* H, int* n, const
   *d_x = e->res[e->cur].x;
   *d_y = e->res[e->cur].y;
   *ready = e->e1;
+}
+
+bool hs_extract_image(hs_extractor* e, int* device, int* W, int* H, const uint8_t** d_img, hipEvent_t* ready) {
+  *device = e->device;
+  *W = e->W;
+  *H = e->H;
+  *d_img = e->d_img;
+  *ready = e->e1;
+  return e->have_img;
 }
 
 hipError_t hs_extract_keys_consumed(hs_extractor* e, hipStream_t consumer) {

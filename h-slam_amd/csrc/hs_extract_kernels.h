@@ -55,3 +55,8 @@ void hs_extract_keys(hs_extractor* e, int* device, int* W, int* H, int* n, const
 // Called by the consumer after it has enqueued its reads on `consumer`: the extractor's next extract waits for them
 // before it reuses the buffers.
 hipError_t hs_extract_keys_consumed(hs_extractor* e, hipStream_t consumer);
+// cvImgL (W*H bytes) where the last extract put it on the device, and the event after which it is complete (the
+// extract's closing event: the same as the keys').  The image is that of the last extract call, also of one that
+// overflowed; the next extract overwrites it, so a consumer waits for its own reads before it returns.  False before
+// the first extract: there is no image yet.
+bool hs_extract_image(hs_extractor* e, int* device, int* W, int* H, const uint8_t** d_img, hipEvent_t* ready);

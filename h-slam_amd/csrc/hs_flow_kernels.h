@@ -1,0 +1,63 @@
+// hs_flow_kernels.h — kernels of include/hs_flow.h: the padded u8 pyramid, its Scharr derivative and the
+// wave-per-point pyramidal Lucas-Kanade tracker.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+constexpr int kFlowWin = 15;        // the window's side
+constexpr int kFlowPad = 15;        // border of every stored level: no window tap lies further outside
+constexpr int kFlowMaxLevels = 3;   // maxLevel 2
+constexpr int kFlowIters = 30;
+
+// One frame's levels in one allocation each: level l is a (w[l] + 30) x (h[l] + 30) array at element `off[l]` of
+// the image buffer (u8, border reflected) and of the derivative buffer (short2 (dx, dy), border zero).
+struct HsFlowLevels {
+  int n;
+  int w[kFlowMaxLevels], h[kFlowMaxLevels];
+  int off[kFlowMaxLevels];
+};
+
+// level 0 with its border from a plain W x H image
+struct HsFlowPadArgs {
+  int w, h;
+  const uint8_t* src;  // w * h
+  uint8_t* dst;        // (w + 30) * (h + 30)
+};
+
+// pyrDown of a padded level into the next padded level, border included
+struct HsFlowDownArgs {
+  int sw, sh, dw, dh;
+  const uint8_t* src;  // (sw + 30) * (sh + 30)
+  uint8_t* dst;        // (dw + 30) * (dh + 30)
+};
+
+struct HsFlowScharrArgs {
+  int w, h;
+  const uint8_t* img;  // (w + 30) * (h + 30)
+  short2* deriv;       // the same shape; zero outside the level
+};
+
+struct HsFlowLkArgs {
+  HsFlowLevels lv;
+  const uint8_t* prev_img;
+  const short2* prev_deriv;
+  const uint8_t* next_img;
+  int n;
+  const float2* prev_xy;
+  const float2* init_xy;  // nullable: no guess
+  float2* xy;
+  uint8_t* status;
+  float* err;
+  uint8_t* good;  // status && err < max_l1_error
+  float max_l1_error;
+  int* n_good;                  // += the good points
+  unsigned long long* n_iters;  // += the iterations run
+};
+
+// the extractor's separate x / y arrays as the (x, y) pairs the tracker reads
+__global__ void hs_k_flow_pack_xy(int n, const float* x, const float* y, float2* xy);
+__global__ void hs_k_flow_pad(HsFlowPadArgs a);
+__global__ void hs_k_flow_pyrdown(HsFlowDownArgs a);
+__global__ void hs_k_flow_scharr(HsFlowScharrArgs a);
+__global__ void hs_k_flow_lk(HsFlowLkArgs a);

@@ -199,6 +199,19 @@ SIGNATURES = {
     "hs_extractor_get": ([VP] * 6, I),
     "hs_extractor_last_stats": ([VP, VP], I),
     "hs_tracer_add_keys": ([VP, VP, I, VP], I),
+    # include/hs_flow.h
+    "hs_flow_create": ([VP, I, I, I, I], I),
+    "hs_flow_destroy": ([VP], None),
+    "hs_flow_set_first": ([VP, VP, I, VP], I),
+    "hs_flow_set_first_extracted": ([VP, VP, VP], I),
+    "hs_flow_track": ([VP, VP, C.c_float, VP], I),
+    "hs_flow_track_extracted": ([VP, VP, C.c_float, VP], I),
+    "hs_flow_track_u8": ([VP, VP, VP, C.c_float, VP], I),
+    "hs_flow_get": ([VP] * 8, I),
+    "hs_flow_mean_flow": ([VP, VP], I),
+    "hs_flow_calc": ([VP, VP, VP, I, VP, VP, VP, VP, VP], I),
+    "hs_flow_get_pyramid": ([VP, I, I, VP, VP, VP, VP], I),
+    "hs_flow_last_stats": ([VP, VP, VP, VP], I),
 }
 
 _lib = None

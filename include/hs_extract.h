@@ -16,7 +16,8 @@
  * The 256-pair sampling pattern (FeatureDetector::pattern) is an argument: H-SLAM passes its own table.
  *
  * Not built: the UseFAST branch (cv::FAST + Ssc), DoSubPix (cv::cornerSubPix), Frame::mGrid, CreateIndPyrs and
- * descriptor matching.
+ * descriptor matching.  The live consumer of the keys and of cvImgL during initialization, Initializer::FindMatches'
+ * Lucas-Kanade tracking, is hs_flow.h, which reads both where an extract left them.
  *
  * The contract, as arithmetic (W x H image, row-major):
  *   Keys.   for y in [19, H-19), then x in [19, W-19): key (x, y) where map[y*W + x] != 0; keys keep that order.
