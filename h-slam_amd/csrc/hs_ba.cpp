@@ -167,6 +167,7 @@ int ensure_capacity(hs_ctx* c, int W, int H, int capP, int capBlk) {
     HS_TRY(dalloc(&s.color, P8)); HS_TRY(dalloc(&s.weight, P8));
     HS_TRY(dalloc(&s.relBL, capP)); HS_TRY(dalloc(&s.nGood, capP));
     HS_TRY(dalloc(&s.r_state, P8)); HS_TRY(dalloc(&s.r_center, P8 * 3));
+    HS_TRY(dalloc(&s.last, (size_t)capP * 2));
   }
   c->cur = 0;
   HS_TRY(dalloc(&c->d_res_of_slot, P8)); HS_TRY(dalloc(&c->d_res_order, P8));
@@ -201,6 +202,9 @@ int ensure_capacity(hs_ctx* c, int W, int H, int capP, int capBlk) {
   HS_TRY(dalloc(&c->d_th_nsurv, 2));
   HS_TRY(dalloc(&c->d_th_surv, HS_TH_SURV));
   HS_TRY(dalloc(&c->d_marg, capP));
+  HS_TRY(dalloc(&c->d_last_tgt, (size_t)capP * 2));
+  HS_TRY(dalloc(&c->d_flag_action, capP));
+  HS_TRY(dalloc(&c->d_flag_counts, 8));
   HS_TRY(dalloc(&c->d_adHTdelta, FF * 8 + 4));  // + cDeltaF
   HS_TRY(dalloc(&c->d_le_chunk, (size_t)(capP + 49) / 50));
   HS_TRY(dalloc(&c->d_le_out, 1));
@@ -1125,6 +1129,7 @@ static int zero_window(hs_ctx* c, int nP) {
     HS_HIP(z(q.u, P * 4)); HS_HIP(z(q.v, P * 4)); HS_HIP(z(q.idepth, P * 4)); HS_HIP(z(q.idepth_zero, P * 4));
     HS_HIP(z(q.priorF, P * 4)); HS_HIP(z(q.color, P8 * 4)); HS_HIP(z(q.weight, P8 * 4));
     HS_HIP(z(q.relBL, P * 4)); HS_HIP(z(q.nGood, P * 4)); HS_HIP(z(q.r_state, P8)); HS_HIP(z(q.r_center, P8 * 12));
+    HS_HIP(hipMemsetAsync(q.last, HS_RES_OOB, P * 2, s));  // lastResiduals: (none, OOB)
   }
   HS_HIP(z(c->d_res_of_slot, P8 * 4)); HS_HIP(z(c->d_res_order, P8)); HS_HIP(z(c->d_pt_host, P * 4));
   HS_HIP(z(c->d_r_active, P8)); HS_HIP(z(c->d_r_energy, P8 * 4)); HS_HIP(z(c->d_r_newEnergy, P8 * 4));
@@ -1286,6 +1291,18 @@ int hs_ba_set_window(hs_ctx* c, const hs_camera* cam, int nF, const hs_frame* fr
       HS_TRY(reset_states(c));
     }
   }
+  // MapPoint::lastResiduals as activation would leave them on this window: slot 0 = (newest frame, the state of
+  // the point's residual into it), slot 1 likewise for the second-newest; (none, OOB) without such a residual
+  std::vector<int8_t> last_tgt((size_t)nP * 2, (int8_t)-1);
+  if (nP > 0) {
+    for (int p = 0; p < nP; p++)
+      for (int k = 0; k < 2; k++)
+        if (c->res_of_slot[(size_t)p * 8 + nF - 1 - k] >= 0) last_tgt[(size_t)p * 2 + k] = (int8_t)(nF - 1 - k);
+    HS_HIP(hipMemcpyAsync(c->d_last_tgt, last_tgt.data(), (size_t)nP * 2, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(hs_k_win_last_tail, dim3((2 * nP + 255) / 256), dim3(256), 0, c->stream, nP, c->d_last_tgt,
+                       c->d_r_state, c->ps[c->cur].last);
+    HS_HIP(hipGetLastError());
+  }
   c->pt_handle.resize(nP);
   for (int i = 0; i < nP; i++) c->pt_handle[i] = i;
   HS_TRY(wait_stream(c));
@@ -1417,6 +1434,11 @@ int hs_ba_fix_linearization(hs_ctx* c, double* energy_out, uint8_t* drop_out, fl
   }
   // linearizeAll(true): no resetOOB (OOB stays sticky from the GN loop), no point step
   HS_TRY(launch_linearize(c, 0, false, true, true));
+  if (nP > 0) {  // lastResiduals[.].second = the states this pass left (Src/FullSystemOptimize.cpp:128-135)
+    hipLaunchKernelGGL(hs_k_win_last_tail, dim3((2 * nP + 255) / 256), dim3(256), 0, c->stream, nP, c->d_last_tgt,
+                       c->d_r_state, c->ps[c->cur].last);
+    HS_HIP(hipGetLastError());
+  }
   HS_TRY(launch_reduce(c, false, true));
   c->haveSystem = true;
   double e = 0.0;
@@ -1651,19 +1673,34 @@ int hs_ba_marginalize_points(hs_ctx* c, int n, const int* points, double* HM_out
   HS_TRY(begin_call(c));
   if (n < 0 || (n > 0 && !points)) return fail(HS_ERR_INVALID, "bad point list");
   HS_HIP(hipSetDevice(c->device));
-  const int nF = c->nF, dim = c->dim();
+  const int dim = c->dim();
   std::vector<uint8_t> flag((size_t)std::max(c->nP, 1), 0);
   for (int i = 0; i < n; i++) {
     if (points[i] < 0 || points[i] >= c->nP) return fail(HS_ERR_INVALID, "point index out of range");
     if (flag[points[i]]) return fail(HS_ERR_INVALID, "duplicate point in the marginalization list");
     flag[points[i]] = 1;
   }
-  // EnergyFunctional::setDeltaF (Src/EnergyFunctional.cpp:128-152) from the device state, in fp32 (hs_k_marg_delta);
   // the flags through the pinned staging, asynchronous (rb_pending: the next rb_stage waits for the copy)
   HS_TRY(c->rb_stage((size_t)c->nP + 1));
   c->rb_pending = true;
   std::memcpy(c->h_rb, flag.data(), (size_t)c->nP);
   if (c->nP > 0) HS_HIP(hipMemcpyAsync(c->d_marg, c->h_rb, c->nP, hipMemcpyHostToDevice, c->stream));
+  HS_TRY(marginalize_flagged(c, n > 0));
+  if (HM_out || bM_out) {
+    HS_TRY(sync_hm(c));
+    c->rb_pending = false;
+    if (HM_out) std::memcpy(HM_out, c->HM.data(), sizeof(double) * dim * dim);
+    if (bM_out) std::memcpy(bM_out, c->bM.data(), sizeof(double) * dim);
+  }
+  return HS_OK;
+}
+
+}  // extern "C"
+
+// the pass of hs_ba_marginalize_points / hs_ba_flag_points_for_removal over the points flagged in d_marg
+int hs::marginalize_flagged(hs_ctx* c, bool any) {
+  const int nF = c->nF, dim = c->dim();
+  // EnergyFunctional::setDeltaF (Src/EnergyFunctional.cpp:128-152) from the device state, in fp32 (hs_k_marg_delta)
   const int nd = nF * nF * 8 + 4;
   hipLaunchKernelGGL(hs_k_marg_delta, dim3((nd + 255) / 256), dim3(256), 0, c->stream, c->d_state, c->d_adHostF,
                      c->d_adTargetF, c->d_adHTdelta);
@@ -1678,18 +1715,14 @@ int hs_ba_marginalize_points(hs_ctx* c, int n, const int* points, double* HM_out
   // the window's linearization is consumed: the caller drops the points (hs_ba_set_window) and relinearizes
   c->haveSystem = false;
   c->hm_host_stale = true;
-  if (c->hm_zero && n > 0) {
+  if (c->hm_zero && any) {
     c->hm_zero = false;
     drop_graph(c);  // the solve's arguments depend on hm_zero
   }
-  if (HM_out || bM_out) {
-    HS_TRY(sync_hm(c));
-    c->rb_pending = false;
-    if (HM_out) std::memcpy(HM_out, c->HM.data(), sizeof(double) * dim * dim);
-    if (bM_out) std::memcpy(bM_out, c->bM.data(), sizeof(double) * dim);
-  }
   return HS_OK;
 }
+
+extern "C" {
 
 // 8x8 inverse: LU with partial pivoting (row swaps recorded), then solve for the identity columns
 static bool inverse8(const double* A, double* Ainv) {
@@ -2165,6 +2198,12 @@ extern "C" int hs_debug_stall(hs_ctx* c, int ms) {
 
 // test hook (not in the header, no device work): whether a W x H window may run hs_k_lin8 (lin8_supported)
 extern "C" int hs_debug_lin8_supported(int W, int H) { return hs::lin8_supported(W, H) ? 1 : 0; }
+// hs::flag_rule (hs_flag_rule.h) on the host: the action in bits 0-1 (0 keep, 1 drop, 2 marginalize), above them the
+// reference's counters the point adds to (4 flag_nores, 8 flag_oob, 16 flag_in, 32 flag_inin)
+extern "C" int hs_debug_flag_rule(int nres, int vis, int nGood, float idepth, float hdif, int last0, int last1,
+                                  int host_flagged) {
+  return hs::flag_rule(nres, vis, nGood, idepth, hdif, last0, last1, host_flagged != 0);
+}
 
 // test hook (not in the header, no device work): device and pinned allocations every hs::Pool of the process has
 // handed out and not yet freed

@@ -52,6 +52,7 @@ struct PointSet {
   int* nGood = nullptr;                       // numGoodResiduals
   uint8_t* r_state = nullptr;                // [cap][8] residual state, slot layout
   float* r_center = nullptr;                  // [cap][8][3] centerProjectedTo
+  uint8_t* last = nullptr;                    // [cap][2] MapPoint::lastResiduals[.].second
 };
 
 // host mirror of the window's structure (the reference's frameHessians / pointHessians / residual lists)
@@ -67,6 +68,17 @@ struct WinPoint {
   int nres = 0;
   int tgt[HS_MAXF];       // residual list (PointHessian::residuals order): target frame keys
   uint8_t st[HS_MAXF];    // 0xFF: a committed residual; else the initial ResState of a residual inserted since
+  // MapPoint::lastResiduals[2]: the target frame's key (-1: none) and where the state comes from at the next commit
+  // (a literal ResState, or HS_WIN_LAST_KEEP | s: the device's slot s).  A residual into a (point, target) pair is
+  // never created twice, so "the slot's residual still exists" (the reference resets .first when it is dropped) is
+  // "the residual list holds the slot's key": no separate reset bookkeeping.
+  int last_key[2] = {-1, -1};
+  uint8_t last_code[2] = {HS_RES_OOB, HS_RES_OOB};
+  bool has_residual_into(int key) const {
+    for (int q = 0; q < nres; q++)
+      if (tgt[q] == key) return true;
+    return false;
+  }
 };
 
 }  // namespace hs
@@ -178,7 +190,10 @@ struct hs_ctx : hs::Device {
   float* d_cand = nullptr;  // [nranks][cand_stride] newest-frame energy per point (-1 / NaN = none)
   int cand_stride = 0;
   bool hm_zero = true;      // marginalization prior not set: the solve skips HM
-  uint8_t* d_marg = nullptr;     // [nP] marginalization flags (hs_ba_marginalize_points)
+  uint8_t* d_marg = nullptr;     // [nP] marginalization flags (hs_ba_marginalize_points, hs_k_win_flag)
+  int8_t* d_last_tgt = nullptr;  // [nP][2] lastResiduals' tail columns of the committed window (hs_k_win_last_tail)
+  uint8_t* d_flag_action = nullptr;  // [nP] hs_k_win_flag's decisions
+  int* d_flag_counts = nullptr;      // [8] its counters
   float* d_adHTdelta = nullptr;  // [nF*nF][8] EnergyFunctional::adHTdeltaF for fixLinearizationF
   float* d_le_chunk = nullptr;   // hs_ba_calc_energies: per-chunk sums
   double* d_le_out = nullptr;
@@ -275,6 +290,8 @@ size_t fstage_bytes();
 int cand_stride_for(hs_ctx* c, int nP, int* stride);
 size_t stage_bytes(int capP);     // hs_ba_window.cpp: pinned commit blob for capP points
 int marginalize_frame_prior(hs_ctx* c, int frame, std::vector<double>& HMn, std::vector<double>& bMn);
+// the marginalization pass over the points flagged in d_marg (any: at least one is): HM / bM updated on the device
+int marginalize_flagged(hs_ctx* c, bool any);
 int commit(hs_ctx* c);            // hs_ba_window.cpp: apply pending structural edits (no-op when clean)
 inline int commit_if_dirty(hs_ctx* c) { return c->dirty ? commit(c) : HS_OK; }
 int max_blocks_for(int capP);

@@ -1302,8 +1302,11 @@ __device__ __forceinline__ void red_host_chunk(const HsRedArgs& a, int h, int q)
     double s = 0.0;
     if (b1 - b0 <= 32) {  // the headline's 32 blocks per host: one 32-wide batch (no clamped duplicate loads)
       float v[32];
+      // (a host without points ahead of the first block, b0 == b1 == 0, clamps to block 0, not to block -1: the
+      // window after flagPointsForRemoval took every point of frame 0 and before that frame is removed)
+      const int bl = max(b1 - 1, 0);
 #pragma unroll
-      for (int u = 0; u < 32; u++) v[u] = a.part[(size_t)min(b0 + u, b1 - 1) * NE64 + e];
+      for (int u = 0; u < 32; u++) v[u] = a.part[(size_t)min(b0 + u, bl) * NE64 + e];
 #pragma unroll
       for (int u = 0; u < 32; u++)
         if (b0 + u < b1) s += (double)v[u];

@@ -11,6 +11,10 @@
 // every point (or its staged data), residual tables, the frame column map, HM / bM -- uploads it with one
 // asynchronous copy, and one gather kernel (hs_win_kernels.hip) moves the device-resident point state into the new
 // order.  No device allocation and no synchronous copy on the keyframe path.
+//
+// MapPoint::lastResiduals[2] rides along: the mirror keeps the two target frames' keys per point, the device the two
+// states (include/hs_ba.h, hs_ba_get_last_residuals).  hs_ba_flag_points_for_removal (System::flagPointsForRemoval,
+// Src/Mapping.cpp:248-328) decides on the device from that state and compacts the mirror by the actions it reads back.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -68,6 +72,12 @@ void mirror_from_committed(hs_ctx* c) {
       w.st[w.nres] = (uint8_t)HS_WIN_KEEP;
       w.nres++;
     }
+    // lastResiduals as hs_ba_set_window derived them: the device's slots, named by the newest two frames' keys
+    for (int k = 0; k < 2; k++) {
+      const int t = c->nF - 1 - k;
+      w.last_key[k] = (t >= 0 && w.has_residual_into(t)) ? t : -1;
+      w.last_code[k] = (uint8_t)(HS_WIN_LAST_KEEP | k);
+    }
     const int h = c->pt_host[p];
     set_loc(c, w.handle, h, (int)c->wpts[h].size());
     c->wpts[h].push_back(w);
@@ -116,7 +126,7 @@ size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 namespace hs {
 size_t stage_bytes(int capP) {
   const size_t n = (size_t)capP;
-  return align16(4 * n) + align16(32 * n) + align16(4 * n) + align16(8 * n) + align16(8 * n) + 64 +
+  return align16(4 * n) + align16(32 * n) + align16(4 * n) + align16(8 * n) + align16(8 * n) + align16(4 * n) + 64 +
          align16(sizeof(HsStagedPoint) * n) + align16(8 * (size_t)HS_MAXDIM * HS_MAXDIM) + align16(8 * HS_MAXDIM) + 256;
 }
 
@@ -191,6 +201,7 @@ int commit(hs_ctx* c) {
   int* pth = (int*)take(4 * (size_t)nP);
   int8_t* rord = (int8_t*)take(8 * (size_t)nP);
   uint8_t* nres = take(8 * (size_t)nP);
+  uint8_t* lastc = take(4 * (size_t)nP);
   int* hpb = (int*)take(64);
   HsStagedPoint* stg = (HsStagedPoint*)take(sizeof(HsStagedPoint) * (size_t)std::max(k, 1));
   double* hm = (double*)take(8 * (size_t)n * n);
@@ -226,6 +237,12 @@ int commit(hs_ctx* c) {
         c->res_target.push_back(t);
         r++;
         w.st[q] = (uint8_t)HS_WIN_KEEP;
+      }
+      for (int k = 0; k < 2; k++) {  // lastResiduals: the state's source, and the column the tail reads
+        lastc[p * 4 + k] = w.last_code[k];
+        const int t = w.last_key[k] >= 0 && w.has_residual_into(w.last_key[k]) ? key_idx[w.last_key[k]] : -1;
+        lastc[p * 4 + 2 + k] = (uint8_t)(int8_t)t;
+        w.last_code[k] = (uint8_t)(HS_WIN_LAST_KEEP | k);
       }
       w.src = p;
       c->pt_host[p] = f;
@@ -264,8 +281,12 @@ int commit(hs_ctx* c) {
   a.staged = (const HsStagedPoint*)dptr(stg);
   const PointSet& F = c->ps[c->cur];
   const PointSet& T = c->ps[c->cur ^ 1];
-  a.from = {F.u, F.v, F.idepth, F.idepth_zero, F.priorF, F.color, F.weight, F.relBL, F.nGood, F.r_state, F.r_center};
-  a.to = {T.u, T.v, T.idepth, T.idepth_zero, T.priorF, T.color, T.weight, T.relBL, T.nGood, T.r_state, T.r_center};
+  a.from = {F.u, F.v, F.idepth, F.idepth_zero, F.priorF, F.color, F.weight, F.relBL, F.nGood, F.r_state, F.r_center,
+            F.last};
+  a.to = {T.u, T.v, T.idepth, T.idepth_zero, T.priorF, T.color, T.weight, T.relBL, T.nGood, T.r_state, T.r_center,
+          T.last};
+  a.lastc = dptr(lastc);
+  a.last_tgt = c->d_last_tgt;
   float* hdif_dst = c->hdif_solved == c->d_p_HdiF ? c->d_p_HdiF_alt : c->d_p_HdiF;
   a.hdif_from = c->hdif_solved;
   a.hdif_to = hdif_dst;
@@ -503,7 +524,15 @@ int hs_ba_insert_residuals(hs_ctx* c, int n, const int* handles, const int* targ
   HS_TRY(ensure_incremental(c));
   for (int i = 0; i < n; i++) {
     WinPoint* w = find_point(c, handles[i]);
-    HS_TRY(add_residual(c, w, w ? c->loc_key[handles[i]] : -1, targets[i], states ? states[i] : (uint8_t)HS_RES_IN));
+    const uint8_t st = states ? states[i] : (uint8_t)HS_RES_IN;
+    HS_TRY(add_residual(c, w, w ? c->loc_key[handles[i]] : -1, targets[i], st));
+    // activation's lastResiduals (Src/FullSystemOptPoint.cpp:142-168): a residual that starts IN into the newest /
+    // second-newest frame of this moment becomes slot 0 / 1
+    const int k = (int)c->wframes.size() - 1 - targets[i];
+    if (st == HS_RES_IN && (k == 0 || k == 1)) {
+      w->last_key[k] = c->wframes[targets[i]].key;
+      w->last_code[k] = (uint8_t)HS_RES_IN;
+    }
   }
   return HS_OK;
 }
@@ -516,6 +545,11 @@ int hs_ba_add_residuals_to_newest(hs_ctx* c, int* n_added) {
   for (int f = 0; f < nF - 1; f++)
     for (auto& w : c->wpts[f]) {
       HS_TRY(add_residual(c, &w, c->wframes[f].key, nF - 1, (uint8_t)HS_RES_IN));
+      // lastResiduals[1] = lastResiduals[0]; lastResiduals[0] = (the new residual, IN) (Src/Mapping.cpp:53-54)
+      w.last_key[1] = w.last_key[0];
+      w.last_code[1] = w.last_code[0];
+      w.last_key[0] = c->wframes[nF - 1].key;
+      w.last_code[0] = (uint8_t)HS_RES_IN;
       cnt++;
     }
   if (n_added) *n_added = cnt;
@@ -719,6 +753,124 @@ int hs_ba_get_point_state(hs_ctx* c, float* idepth, float* idepth_zero, float* r
   c->rb_pending = false;
   for (int k = 0; k < 5; k++)
     if (dst[k]) std::memcpy(dst[k], c->h_rb + k * n * 4, n * 4);
+  return HS_OK;
+}
+
+int hs_ba_get_last_residuals(hs_ctx* c, int* target, uint8_t* state) {
+  HS_TRY(ensure_incremental(c));
+  HS_TRY(commit_if_dirty(c));
+  const size_t n = c->nP;
+  if (n == 0) return HS_OK;
+  if (target) {  // the mirror names the frames; a slot whose residual left the point's list has none
+    size_t p = 0;
+    for (int f = 0; f < (int)c->wframes.size(); f++)
+      for (const WinPoint& w : c->wpts[f]) {
+        for (int k = 0; k < 2; k++)
+          target[p * 2 + k] = w.last_key[k] >= 0 && w.has_residual_into(w.last_key[k]) ? frame_index(c, w.last_key[k]) : -1;
+        p++;
+      }
+  }
+  if (state) {
+    HS_TRY(c->rb_stage(n * 2));
+    c->rb_pending = true;
+    HS_HIP(hipMemcpyAsync(c->h_rb, c->ps[c->cur].last, n * 2, hipMemcpyDeviceToHost, c->stream));
+    HS_TRY(wait_stream(c));
+    c->rb_pending = false;
+    std::memcpy(state, c->h_rb, n * 2);
+  }
+  return HS_OK;
+}
+
+int hs_ba_set_last_residuals(hs_ctx* c, int n, const int* handles, const int* target, const uint8_t* state) {
+  if (n < 0 || (n > 0 && (!handles || !target || !state))) return fail(HS_ERR_INVALID, "bad lastResiduals list");
+  HS_TRY(ensure_incremental(c));
+  const int nF = (int)c->wframes.size();
+  for (int i = 0; i < n; i++) {
+    if (!find_point(c, handles[i])) return fail(HS_ERR_INVALID, "unknown point handle");
+    for (int k = 0; k < 2; k++) {
+      if (target[i * 2 + k] < -1 || target[i * 2 + k] >= nF) return fail(HS_ERR_INVALID, "bad lastResiduals target");
+      if (state[i * 2 + k] > HS_RES_OUT) return fail(HS_ERR_INVALID, "bad lastResiduals state");
+    }
+  }
+  for (int i = 0; i < n; i++) {
+    WinPoint* w = find_point(c, handles[i]);
+    for (int k = 0; k < 2; k++) {
+      w->last_key[k] = target[i * 2 + k] < 0 ? -1 : c->wframes[target[i * 2 + k]].key;
+      w->last_code[k] = state[i * 2 + k];
+    }
+  }
+  if (n > 0) c->dirty = true;
+  return HS_OK;
+}
+
+// System::flagPointsForRemoval (Src/Mapping.cpp:248-328): hs_k_win_flag decides on the committed window from the
+// device-resident point state; apply = 1 then runs marginalizePointsF over the marginalized points (the pass of
+// hs_ba_marginalize_points, its flags already on the device) and compacts the mirror as the reference compacts
+// pointHessians.  One small read-back (the actions and counters): the mirror has to learn which points left.
+int hs_ba_flag_points_for_removal(hs_ctx* c, int n_marg_frames, const int* marg_frames, int apply, uint8_t* action_out,
+                                  int* counts_out, double* HM_out, double* bM_out) {
+  if (!c) return fail(HS_ERR_INVALID, "null context");
+  if (c->comm_lost) return fail(HS_ERR_RCCL, "communicator aborted by an earlier call (a peer rank failed)");
+  if (c->multi_rank()) return fail(HS_ERR_STATE, "hs_ba_flag_points_for_removal needs a single-rank context");
+  if (n_marg_frames < 0 || n_marg_frames > HS_MAXF || (n_marg_frames > 0 && !marg_frames))
+    return fail(HS_ERR_INVALID, "bad frame list");
+  HS_TRY(ensure_incremental(c));
+  HS_TRY(commit_if_dirty(c));
+  if (c->nF == 0) return fail(HS_ERR_STATE, "no window");
+  unsigned mask = 0;
+  for (int i = 0; i < n_marg_frames; i++) {
+    if (marg_frames[i] < 0 || marg_frames[i] >= c->nF) return fail(HS_ERR_INVALID, "frame index out of range");
+    mask |= 1u << marg_frames[i];
+  }
+  const int nP = c->nP;
+  // the counters [8 ints] and the actions [nP] through the pinned staging
+  HS_TRY(c->rb_stage(32 + (size_t)std::max(nP, 1)));
+  int* h_counts = reinterpret_cast<int*>(c->h_rb);
+  const uint8_t* h_action = c->h_rb + 32;
+  std::memset(c->h_rb, 0, 32);
+  if (nP > 0) {
+    HsWinFlagArgs a;
+    a.n = nP;
+    a.marg_mask = mask;
+    a.idepth = c->d_idepth;
+    a.nGood = c->d_fix_nGood;
+    a.hdif = c->hdif_solved;
+    a.pt_host = c->d_pt_host;
+    a.r_state = c->d_r_state;
+    a.res_order = c->d_res_order;
+    a.last = c->ps[c->cur].last;
+    a.action = c->d_flag_action;
+    a.marg = c->d_marg;
+    a.counts = c->d_flag_counts;
+    HS_HIP(hipMemsetAsync(c->d_flag_counts, 0, 32, c->stream));
+    hipLaunchKernelGGL(hs_k_win_flag, dim3((nP + 255) / 256), dim3(256), 0, c->stream, a);
+    HS_HIP(hipGetLastError());
+    c->rb_pending = true;
+    HS_HIP(hipMemcpyAsync(c->h_rb, c->d_flag_counts, 32, hipMemcpyDeviceToHost, c->stream));
+    HS_HIP(hipMemcpyAsync(c->h_rb + 32, c->d_flag_action, nP, hipMemcpyDeviceToHost, c->stream));
+    HS_TRY(wait_stream(c));
+    c->rb_pending = false;
+  }
+  if (action_out && nP > 0) std::memcpy(action_out, h_action, nP);
+  if (counts_out) std::memcpy(counts_out, h_counts, 6 * sizeof(int));
+  if (apply) {
+    // without a marginalized point HM / bM / hm_zero stay as they are (marginalizePointsF over an empty set)
+    if (h_counts[5] > 0) HS_TRY(marginalize_flagged(c, true));
+    // the removals in flagPointsForRemoval's order, while the pass runs (a committed point's src is its position)
+    if (h_counts[4] + h_counts[5] > 0) {
+      for (int f = 0; f < (int)c->wframes.size(); f++)
+        compact_list(c, f, [&](const WinPoint& w) { return h_action[w.src] != 0; }, nullptr);
+      c->dirty = true;
+    }
+  }
+  if (HM_out || bM_out) {
+    HS_TRY(sync_hm(c));
+    const int n = c->dim();
+    if ((int)c->HM.size() != n * n) c->HM.assign((size_t)n * n, 0.0);
+    if ((int)c->bM.size() != n) c->bM.assign(n, 0.0);
+    if (HM_out) std::memcpy(HM_out, c->HM.data(), sizeof(double) * n * n);
+    if (bM_out) std::memcpy(bM_out, c->bM.data(), sizeof(double) * n);
+  }
   return HS_OK;
 }
 

@@ -10,6 +10,8 @@
 //   hs_k_win_newest   the BA -> tracker hand-off (CoarseTracker::makeCoarseDepthL0's point loop,
 //                     Src/CoarseTracker.cpp:110-129): the points whose residual into the newest frame is IN, in point
 //                     order, as (centerProjectedTo u, v, idepth, HdiF); one workgroup, ballot prefix sums per chunk.
+//   hs_k_win_last_tail  MapPoint::lastResiduals[.].second after the optimize tail (the commit carries the pairs along).
+//   hs_k_win_flag     System::flagPointsForRemoval's per-point decision (hs_flag_rule.h) and its counters.
 #include <hip/hip_runtime.h>
 
 #include "hs_win_kernels.h"
@@ -70,6 +72,59 @@ __global__ __launch_bounds__(256) void hs_k_win_gather(HsWinGatherArgs a) {
   a.to.r_center[3 * o] = c0;
   a.to.r_center[3 * o + 1] = c1;
   a.to.r_center[3 * o + 2] = c2;
+  // lastResiduals slot t: the state an old slot holds, or a literal one; its tail column for the new layout
+  if (t < 2) {
+    const unsigned lc = a.lastc[(size_t)p * 4 + t];
+    uint8_t ls = (uint8_t)(lc & 3u);
+    if ((lc & HS_WIN_LAST_KEEP) && src >= 0) ls = a.from.last[(size_t)src * 2 + (lc & 1u)];
+    a.to.last[(size_t)p * 2 + t] = ls;
+    a.last_tgt[(size_t)p * 2 + t] = (int8_t)a.lastc[(size_t)p * 4 + 2 + t];
+  }
+}
+
+// The optimize tail's lastResiduals update (System::linearizeAll(true), Src/FullSystemOptimize.cpp:128-135): a slot
+// whose residual is still in the window takes that residual's state.  One lane per (point, slot).
+__global__ __launch_bounds__(256) void hs_k_win_last_tail(int n, const int8_t* __restrict__ last_tgt,
+                                                          const uint8_t* __restrict__ r_state,
+                                                          uint8_t* __restrict__ last) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * n) return;
+  const int t = last_tgt[i];
+  if (t >= 0 && t < HS_MAXF) last[i] = r_state[(size_t)(i >> 1) * 8 + t];
+}
+
+// System::flagPointsForRemoval (Src/Mapping.cpp:248-328): one lane per point applies hs::flag_rule to the point's
+// device-resident state.  The residual list and the slot states are one 8-byte row each.  Every lane stays for the
+// ballots; the counters are integers, so the order of the waves' atomics does not matter.
+__global__ __launch_bounds__(256) void hs_k_win_flag(HsWinFlagArgs a) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  int code = -1;
+  if (p < a.n) {
+    const unsigned long long ord = reinterpret_cast<const unsigned long long*>(a.res_order)[p];
+    const unsigned long long st = reinterpret_cast<const unsigned long long*>(a.r_state)[p];
+    int nres = 0, vis = 0;
+    for (int q = 0; q < 8; q++) {
+      const int t = (int)(int8_t)(ord >> (8 * q));
+      if (t < 0 || t >= HS_MAXF) break;
+      nres++;
+      if (((a.marg_mask >> t) & 1u) && (uint8_t)(st >> (8 * t)) == HS_RES_IN) vis++;
+    }
+    const unsigned l = reinterpret_cast<const unsigned short*>(a.last)[p];
+    const int h = a.pt_host[p];
+    const bool host_flagged = h >= 0 && h < HS_MAXF && ((a.marg_mask >> h) & 1u);
+    code = hs::flag_rule(nres, vis, a.nGood[p], a.idepth[p], a.hdif[p], (int)(l & 0xffu), (int)(l >> 8), host_flagged);
+    const int act = code & hs::HS_FLAG_ACTION;
+    a.action[p] = (uint8_t)act;
+    a.marg[p] = act == hs::HS_FLAG_MARG ? 1 : 0;
+  }
+  const bool on = code >= 0;
+  const bool bit[6] = {on && (code & hs::HS_FLAG_NORES), on && (code & hs::HS_FLAG_OOB), on && (code & hs::HS_FLAG_IN),
+                       on && (code & hs::HS_FLAG_ININ), on && (code & hs::HS_FLAG_ACTION) == hs::HS_FLAG_DROP,
+                       on && (code & hs::HS_FLAG_ACTION) == hs::HS_FLAG_MARG};
+  for (int k = 0; k < 6; k++) {
+    const int cnt = __popcll(__ballot(bit[k]));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&a.counts[k], cnt);
+  }
 }
 
 // points p (in order) with res_of_slot[p][newest] >= 0 and state IN -> out[cap * {0,1,2,3}] = cu, cv, cid, HdiF

@@ -105,6 +105,11 @@ SIGNATURES = {
     "hs_ba_get_marginal_prior": ([VP, VP, VP], I),
     "hs_ba_synchronize": ([VP], I),
     "hs_ba_get_point_state": ([VP] * 6, I),
+    "hs_ba_get_last_residuals": ([VP, VP, VP], I),
+    "hs_ba_set_last_residuals": ([VP, I, VP, VP, VP], I),
+    "hs_ba_flag_points_for_removal": ([VP, I, VP, I, VP, VP, VP, VP], I),
+    # test hook (not in the header): the per-point rule of hs_ba_flag_points_for_removal on the host
+    "hs_debug_flag_rule": ([I, I, I, C.c_float, C.c_float, I, I, I], I),
     "hs_debug_state_size": ([], I),
     "hs_debug_get_state": ([VP, VP], I),
     "hs_debug_nullspace_error": ([VP, VP], I),

@@ -234,6 +234,39 @@ class BAWindow:
                                                                              "numGoodResiduals", "HdiF")]))
         return o
 
+    def lastResiduals(self):
+        """MapPoint::lastResiduals in window order: dict(target [n][2] window frame index (-1: no residual),
+        state [n][2]); [:, 0] is the latest."""
+        self._sync()
+        o = dict(target=np.zeros((self.n_points, 2), np.int32), state=np.zeros((self.n_points, 2), np.uint8))
+        check(self.lib.hs_ba_get_last_residuals(self.h, ptr(o["target"]), ptr(o["state"])))
+        return o
+
+    def setLastResiduals(self, handles, target, state):
+        """lastResiduals of the points `handles`: target [n][2] window frame index or -1, state [n][2]."""
+        hd = np.ascontiguousarray(handles, np.int32)
+        tg = np.ascontiguousarray(target, np.int32).reshape(len(hd), 2)
+        st = np.ascontiguousarray(state, np.uint8).reshape(len(hd), 2)
+        check(self.lib.hs_ba_set_last_residuals(self.h, len(hd), ptr(hd), ptr(tg), ptr(st)))
+
+    def flagPointsForRemoval(self, marg_frames, apply=True, return_prior=False):
+        """System::flagPointsForRemoval (+ marginalizePointsF and the removals with apply) decided on the device.
+        marg_frames: the window frames flagged for marginalization.  Returns dict(action [n] (0 keep, 1 drop,
+        2 marginalize; window order as of the call), counts (flag_nores, flag_oob, flag_in, flag_inin, n_drop,
+        n_marg), and with return_prior HM, bM)."""
+        self._sync()
+        mf = np.ascontiguousarray(marg_frames, np.int32).reshape(-1)
+        act = np.zeros(self.n_points, np.uint8)
+        cnt = np.zeros(6, np.int32)
+        HM, bM = (np.zeros((self.dim, self.dim)), np.zeros(self.dim)) if return_prior else (None, None)
+        check(self.lib.hs_ba_flag_points_for_removal(self.h, len(mf), ptr(mf), int(bool(apply)), ptr(act), ptr(cnt),
+                                                     ptr(HM), ptr(bM)))
+        o = dict(action=act, counts=dict(zip(("flag_nores", "flag_oob", "flag_in", "flag_inin", "n_drop", "n_marg"),
+                                             map(int, cnt))))
+        if return_prior:
+            o.update(HM=HM, bM=bM)
+        return o
+
     def synchronize(self):
         check(self.lib.hs_ba_synchronize(self.h))
 

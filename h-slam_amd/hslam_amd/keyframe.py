@@ -15,7 +15,9 @@ driver (``KeyframeBA``) that runs, per keyframe, what AddKeyframe does around th
 
 The System-level decisions (which frame to marginalize, flagPointsForRemoval's per-point tests, the lastResiduals
 bookkeeping) are the caller's code in the reference too; they run here in numpy and are not part of the timed library
-work.  Frame policy: the window holds ``window`` keyframes during optimize and the oldest is marginalized afterwards
+work.  KeyframeBA(decisions="device") hands flagPointsForRemoval to the library instead: one
+hs_ba_flag_points_for_removal call decides on the device (the context keeps lastResiduals itself), runs
+marginalizePointsF and removes the points; that call is timed with the library work.  Frame policy: the window holds ``window`` keyframes during optimize and the oldest is marginalized afterwards
 (flagFramesForMarginalization's steady state; its distance score and point-count rules are not modelled).
 """
 from __future__ import annotations
@@ -146,7 +148,13 @@ class KeyframeBA:
     """System::AddKeyframe's BA part over a BASequence, through the incremental C-ABI (module docstring)."""
 
     def __init__(self, seq: BASequence, device: int = 0, window: int = 8, capacity: int = 0, params=None,
-                 tracker=None, image_path: str = "raw", iters: int = 6, allow_break: bool = False):
+                 tracker=None, image_path: str = "raw", iters: int = 6, allow_break: bool = False,
+                 decisions: str = "host"):
+        if decisions not in ("host", "device"):
+            raise ValueError("decisions must be 'host' or 'device'")
+        # flagPointsForRemoval: "host" decides here in numpy from read-backs (the module docstring's caller code);
+        # "device" is one hs_ba_flag_points_for_removal call (the library keeps lastResiduals itself)
+        self.decisions = decisions
         self.seq = seq
         self.window = window
         self.iters = iters
@@ -201,8 +209,9 @@ class KeyframeBA:
         newest, second = len(self.frames) - 1, len(self.frames) - 2
         for j, hd in enumerate(handles):
             self.cand_of[int(hd)] = (host_k, int(idx[j]))
-            self.last_state[int(hd)] = [RES_IN if ok[j, newest] else RES_OOB,
-                                        RES_IN if second >= 0 and ok[j, second] else RES_OOB]
+            if self.decisions == "host":
+                self.last_state[int(hd)] = [RES_IN if ok[j, newest] else RES_OOB,
+                                            RES_IN if second >= 0 and ok[j, second] else RES_OOB]
         return handles
 
     # ---------------------------------------------------------------- the sequence
@@ -223,6 +232,7 @@ class KeyframeBA:
         self.marg_points), 'points_marginalized' (after it) and 'frame_marginalized' (after marginalizeFrame of
         self.marg_frame): parity tests rebuild the window there.  Returns dict of per-phase seconds."""
         ba, timer = self.ba, _Timer()
+        host_rule = self.decisions == "host"
         wall0 = time.perf_counter()
         # insertFrame, new residuals of the old points, activation of the previous newest KF's points
         self._insert_frame(k, timer)
@@ -241,14 +251,15 @@ class KeyframeBA:
         if check:
             check(self, "tail")
         # lastResiduals[.].second from the tail's states (System::linearizeAll(true), Src/FullSystemOptimize.cpp:128)
-        st = ba.structure()
-        res = ba.residuals()
-        handles = st["handles"]
-        newest, second = len(self.frames) - 1, len(self.frames) - 2
-        for r in np.nonzero((st["res_target"] == newest) | (st["res_target"] == second))[0]:
-            hd = int(handles[st["res_point"][r]])
-            self.last_state[hd][0 if st["res_target"][r] == newest else 1] = int(res["state"][r])
-        hdif = tail["HdiF"]
+        if host_rule:
+            st = ba.structure()
+            res = ba.residuals()
+            handles = st["handles"]
+            newest, second = len(self.frames) - 1, len(self.frames) - 2
+            for r in np.nonzero((st["res_target"] == newest) | (st["res_target"] == second))[0]:
+                hd = int(handles[st["res_point"][r]])
+                self.last_state[hd][0 if st["res_target"][r] == newest else 1] = int(res["state"][r])
+            hdif = tail["HdiF"]
         # toRemove, removeOutliers, the tracker's new reference
         timer.run("post", ba.dropInactiveResiduals)
         gone = timer.run("post", ba.removeOutliers)
@@ -259,7 +270,27 @@ class KeyframeBA:
             timer.run("post", self.tracker.set_ref_ba, ba, self.image_path in ("device", "device_ptr"))
         # flagPointsForRemoval (Src/Mapping.cpp:248-328), the frame to marginalize: the oldest once the window is full
         info = dict(energies=energies, iters=n_it, n_points=ba.n_points, n_res=ba.n_res, dropped_points=len(gone))
-        if marginalize and len(self.frames) >= self.window:
+        if marginalize and len(self.frames) >= self.window and not host_rule:
+            # the decisions, marginalizePointsF and the removals in one library call; only the actions come back
+            marg_f = 0
+            hd_all = ba.structure()["handles"]
+            self.marg_points, self.marg_frame = None, marg_f  # the points are known after the call
+            if check:
+                check(self, "marginalize")
+            flg = self.last_flags = timer.run("post", ba.flagPointsForRemoval, [marg_f], True, False)
+            marg, drop = flg["action"] == 2, flg["action"] == 1
+            self.marg_points = np.nonzero(marg)[0].astype(np.int32)
+            self.marg_handles, self.drop_handles = hd_all[marg], hd_all[drop]
+            if check:
+                check(self, "points_marginalized")
+            for hd in hd_all[marg | drop]:
+                self.cand_of.pop(int(hd), None)
+            timer.run("post", ba.removeFrame, marg_f, True)
+            self.frames.pop(marg_f)
+            if check:
+                check(self, "frame_marginalized")
+            info.update(marginalized_points=int(marg.sum()), dropped=int(drop.sum()))
+        elif marginalize and len(self.frames) >= self.window:
             marg_f = 0
             st = ba.structure()
             ps = ba.point_state()
@@ -286,6 +317,7 @@ class KeyframeBA:
             drop = drop_now | (flag & ~marg)
             mpos = np.nonzero(marg)[0].astype(np.int32)
             self.marg_points, self.marg_frame = mpos, marg_f
+            self.marg_handles, self.drop_handles = hd_all[marg], hd_all[drop]
             if check:
                 check(self, "marginalize")  # before marginalizePointsF: the window as the tail and drops left it
             if len(mpos):

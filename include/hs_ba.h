@@ -35,6 +35,8 @@
  *   hs_ba_marginalize_points    System::flagPointsForRemoval (per-point part) + EnergyFunctional::marginalizePointsF
  *                               (Src/Mapping.cpp:280-293; Src/EnergyFunctional.cpp:545-609).
  *   hs_ba_marginalize_frame     EnergyFunctional::marginalizeFrame (Src/EnergyFunctional.cpp:456-543).
+ *   hs_ba_flag_points_for_removal   System::flagPointsForRemoval (Src/Mapping.cpp:248-328) + marginalizePointsF,
+ *                               decided on the device from the window's own point state.
  *   hs_comm_*                   (new) RCCL communicator for point-sharded windows; one rank per GPU.
  */
 #ifndef HS_BA_H
@@ -234,6 +236,42 @@ int hs_ba_get_point_state(hs_ctx* ctx, float* idepth, float* idepth_zero, float*
    res_target[nR] (targets in activeResiduals order: points in window order, each point's list in order).
    All nullable. */
 int hs_ba_get_structure(hs_ctx* ctx, int* handles, int* pt_host, int* nres, int* res_target);
+
+/* MapPoint::lastResiduals[2] = (residual, ResState) pairs, [0] the latest, kept by the context per point:
+     activation (Src/FullSystemOptPoint.cpp:142-168): both slots start (none, OOB); hs_ba_insert_residuals of a
+       residual in state IN into the window's newest frame at the time of that call sets slot 0 = (that frame, IN), one
+       into the second-newest frame slot 1 likewise;
+     hs_ba_add_residuals_to_newest (Src/Mapping.cpp:53-54): slot 1 = slot 0, slot 0 = (newest, IN) for every point
+       that got a residual;
+     hs_ba_fix_linearization (Src/FullSystemOptimize.cpp:128-135): a slot whose residual is still in the window takes
+       that residual's state after the tail; a slot whose residual was dropped (hs_ba_drop_residuals,
+       hs_ba_drop_inactive_residuals, hs_ba_remove_frame: the reference's .first.reset()) keeps its last state.
+       A residual into a (point, target) pair is never created twice (duplicates are rejected, only the newest frame
+       receives new residuals), so "the slot's residual exists" is "the point's list holds a residual into the slot's
+       frame": there is no separate reset bookkeeping;
+     hs_ba_set_window: derived as activation would from the window as given: slot 0 = (newest, its state) if the point
+       has a residual into the newest frame, else (none, OOB); slot 1 likewise for the second-newest.
+   The pairs live on the device and follow their points through commits.
+   hs_ba_get_last_residuals (window order, commits first, both nullable): target[nP][2] the window index of the slot's
+   frame, -1 when the slot has no residual (any more); state[nP][2].
+   hs_ba_set_last_residuals: the pairs of n points by handle (target[n][2] window frame index or -1, state[n][2]), for
+   a caller restoring a saved window; applied by the next commit. */
+int hs_ba_get_last_residuals(hs_ctx* ctx, int* target, uint8_t* state);
+int hs_ba_set_last_residuals(hs_ctx* ctx, int n, const int* handles, const int* target, const uint8_t* state);
+
+/* System::flagPointsForRemoval (Src/Mapping.cpp:248-328) on the committed window; marg_frames: the window frames
+   with FlaggedForMarginalization.  action_out[nP] (window order as of this call): 0 keep, 1 drop (OUTLIER), 2 marginalize.
+   counts_out[6]: flag_nores, flag_oob, flag_in, flag_inin (the reference's counters), n_drop, n_marg.
+   Per point (isOOB / isInlierNew, Include/MapPoint.h:133-161; numGoodResiduals, idepth and the last solve's HdiF as
+   hs_ba_get_point_state returns them, idepth_hessian = 1 / HdiF in fp64, lastResiduals as above): the decision runs
+   on the device, nothing but action_out / counts_out is read back.
+   apply = 0: decisions only, nothing changes.  apply = 1: the marginalization pass of hs_ba_marginalize_points over
+   the action-2 points (HM / bM updated; HM_out / bM_out nullable), then every action != 0 point leaves the window as
+   hs_ba_remove_points removes it.  Without an action-2 point HM / bM stay exactly as they were.
+   Single-rank contexts only: with a communicator or in a rank group the call returns HS_ERR_STATE.  A frame index
+   outside the window returns HS_ERR_INVALID.  All outputs nullable. */
+int hs_ba_flag_points_for_removal(hs_ctx* ctx, int n_marg_frames, const int* marg_frames, int apply,
+                                  uint8_t* action_out, int* counts_out, double* HM_out, double* bM_out);
 
 /* multi-GPU (point sharding): 128-byte RCCL unique id from rank 0, broadcast by the caller.
    hs_comm_init must be called before hs_ba_set_window.  Each rank loads its own point shard (same frames);
