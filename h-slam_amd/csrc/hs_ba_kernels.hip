@@ -35,22 +35,8 @@ namespace {
 constexpr float SCALE_F = 50.0f, SCALE_C = 50.0f, SCALE_IDEPTH = 1.0f;
 constexpr int Q_N = 17;  // per-pixel quantities summed over the pattern
 
-// getInterpolatedElement33 (Include/GlobalTypes.h:377-388) on float4 texels
-__device__ __forceinline__ float3 interp33(const float4* __restrict__ img, float x, float y, int w) {
-  int ix = (int)x, iy = (int)y;
-  float dx = x - ix, dy = y - iy, dxdy = dx * dy;
-  const float4* bp = img + ix + iy * w;
-  const float4 p00 = bp[0], p10 = bp[1], p01 = bp[w], p11 = bp[w + 1];
-  const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-  float3 r;
-  r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
-  r.y = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
-  r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
-  return r;
-}
-
-// the same on the packed 12-byte (I, dx, dy) texels of an image slot (HsLinArgs.img3): the 2x2 taps span fewer
-// cache lines than the float4 texels
+// getInterpolatedElement33 (Include/GlobalTypes.h:377-388) on the packed 12-byte (I, dx, dy) texels of an image slot
+// (HsLinArgs.img3): the 2x2 taps span fewer cache lines than the float4 texels
 __device__ __forceinline__ float3 interp33p(const float* __restrict__ img3, float x, float y, int w) {
   int ix = (int)x, iy = (int)y;
   float dx = x - ix, dy = y - iy, dxdy = dx * dy;
@@ -65,18 +51,6 @@ __device__ __forceinline__ float3 interp33p(const float* __restrict__ img3, floa
   r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
   return r;
 }
-#ifndef LIN_ONE_PATH
-#define LIN_ONE_PATH 1
-#endif
-#ifndef LIN_TEXEL12
-#define LIN_TEXEL12 1  // hs_k_lin's taps from the packed 12-byte texels
-#endif
-
-// wall-clock checkpoint of a block (thread 0) when tracing is enabled
-#define HS_TRACE(A, slot)                                                                          \
-  do {                                                                                             \
-    if ((A).trace && threadIdx.x == 0) (A).trace[(size_t)blockIdx.x * 16 + (slot)] = wall_clock64(); \
-  } while (0)
 
 // a double moved between lanes of a row of 16 by one DPP control (quad_perm / row_half_mirror / row_mirror)
 template <int CTRL>
@@ -312,8 +286,7 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
   const float colorK = in.colorK, weightK = in.weightK;
   const HsPrecalc pc = K.pre[tc_];
   // the target's image: selected from the kernel-argument pointers (uniform SGPRs), not loaded per lane
-  const float4* timg = a.img + (long long)hs_img_slot(a.img_slot, tc_) * a.img_stride;  // past the window: frame 0
-  const float* timg3 = a.img3 + (long long)hs_img_slot(a.img_slot, tc_) * a.img_stride * 3;
+  const float* timg3 = a.img3 + (long long)hs_img_slot(a.img_slot, tc_) * a.img_stride * 3;  // past the window: frame 0
   // the point's 8 residual-list slots and previous active mask, as scalars (uniform per point)
   const uint2 ro2 = make_uint2(__builtin_amdgcn_readfirstlane(in.ro2.x), __builtin_amdgcn_readfirstlane(in.ro2.y));
   auto res_slot = [&](int q) -> int { return (int)(int8_t)(((q < 4 ? ro2.x : ro2.y) >> (8 * (q & 3))) & 0xffu); };
@@ -443,8 +416,7 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     q2 = q2 + pc.Kt[2] * idep;
     const float PKu = q0 / q2, PKv = q1 / q2;
     const bool okP = okC && (PKu > 1.1f && PKv > 1.1f && PKu < (cal.W - 3) && PKv < (cal.H - 3));
-    float3 hit = LIN_TEXEL12 ? interp33p(timg3, okP ? PKu : 2.f, okP ? PKv : 2.f, cal.W)
-                             : interp33(timg, okP ? PKu : 2.f, okP ? PKv : 2.f, cal.W);
+    float3 hit = interp33p(timg3, okP ? PKu : 2.f, okP ? PKv : 2.f, cal.W);
     if (trc && threadIdx.x == 0 && hit.x != -12345.f) trc[(size_t)blockIdx.x * 16 + 13] = wall_clock64();
     const float color = colorK;
     const float residual = hit.x - (float)(pc.aff[0] * color + pc.aff[1]);
@@ -849,7 +821,7 @@ __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
   if (work) lin_load(a, pb + wv, lane, cur);  // in flight across the barrier
   __syncthreads();
   HS_TRACE(T, 12);
-  if (work && LIN_ONE_PATH && pb + wv + a.W >= pe) {
+  if (work && pb + wv + a.W >= pe) {
     // the wave's only point (the 2k headline: one point per wave): no loop, so nothing is hoisted out of one and
     // kept live (spilled) across the point's work
     LinPt P;

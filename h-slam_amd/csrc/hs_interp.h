@@ -1,5 +1,5 @@
 // hs_interp.h — the reference's image interpolators (Include/GlobalTypes.h:355-401) on float4 level-0 images
-// (I, dI/dx, dI/dy, 0), shared by the immature-point kernels.  Include inside a file compiled with
+// (I, dI/dx, dI/dy, 0), shared by the immature-point and refinement kernels.  Include inside a file compiled with
 // `#pragma clang fp contract(off)`: the operation order is the reference's.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +31,20 @@ __device__ __forceinline__ float3 interp33(const float4* __restrict__ img, float
   const float dx = x - ix, dy = y - iy, dxdy = dx * dy;
   const float4* bp = img + clamp_base(ix, iy, W, H);
   const float4 p00 = bp[0], p10 = bp[1], p01 = bp[W], p11 = bp[W + 1];
+  const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
+  float3 r;
+  r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
+  r.y = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
+  r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
+  return r;
+}
+
+// the same without the clamp, for callers that pass in-bounds coordinates only
+__device__ __forceinline__ float3 interp33_unclamped(const float4* __restrict__ img, float x, float y, int w) {
+  int ix = (int)x, iy = (int)y;
+  float dx = x - ix, dy = y - iy, dxdy = dx * dy;
+  const float4* bp = img + ix + iy * w;
+  const float4 p00 = bp[0], p10 = bp[1], p01 = bp[w], p11 = bp[w + 1];
   const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
   float3 r;
   r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;

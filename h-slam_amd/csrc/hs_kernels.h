@@ -11,11 +11,14 @@ constexpr int HS_SOLVE_NT = 512;   // hs_k_solve workgroup size
 constexpr int HS_STITCH_NT = 1024; // hs_k_stitch workgroup size
 constexpr int HS_LIN_NW = 8;       // hs_k_lin waves per block (production: each takes points; exact mode: wave 0)
 constexpr int HS_LIN_NT = 64 * HS_LIN_NW;
-#ifndef HS_LIN8_WAVES
-#define HS_LIN8_WAVES 8  // one workgroup per CU (its LDS): waves wv and wv + 4 share a SIMD (hs_k_lin8's L8_PRIO)
-#endif
+constexpr int HS_LIN8_WAVES = 8;  // one workgroup per CU (its LDS): waves wv and wv + 4 share a SIMD (hs_k_lin8's turns)
 constexpr int HS_LIN8_NT = 64 * HS_LIN8_WAVES;  // hs_k_lin8 workgroup size (8 points per wave at a time)
-constexpr int HS_NNS = 7;         // gauge nullspaces: 6 pose + 1 scale (System::getNullspaces)
+// wall-clock checkpoint of a block (thread 0) when tracing is enabled
+#define HS_TRACE(A, slot)                                                                          \
+  do {                                                                                             \
+    if ((A).trace && threadIdx.x == 0) (A).trace[(size_t)blockIdx.x * 16 + (slot)] = wall_clock64(); \
+  } while (0)
+constexpr int HS_NNS = 7;        // gauge nullspaces: 6 pose + 1 scale (System::getNullspaces)
 // The adjoint buffers (fp64 d_adHost / d_adTarget, fp32 d_adHostF / d_adTargetF: [HS_MAXF^2][64]) carry one stamp word
 // after the adjoints: hs_k_fix_frames writes the upload's sequence number there (the fp32 buffers its bits) and into
 // a separate expectation word, and every reader launch (hs_k_stitch: fp64, hs_k_solve: fp32) compares the two.  A

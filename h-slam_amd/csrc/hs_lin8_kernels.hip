@@ -43,60 +43,22 @@ __host__ __device__ constexpr DSlot d_slot(int o1, int o2) {
   return DSlot{-1, -1};
 }
 constexpr float SCALE_F8 = 50.0f, SCALE_C8 = 50.0f, SCALE_IDEPTH8 = 1.0f;
-constexpr int L8_NW = HS_LIN8_NT / 64;  // waves per block
+constexpr int NW8 = HS_LIN8_NT / 64;  // waves per block
 constexpr int NTOP = 91;  // AccumulatorApprox entries of one (host, target) block: Data 55 | TopRight 30 | BotRight 6
 constexpr int Q8_N = 17;  // per-pixel quantities summed over the pattern
-#ifndef L8_TAP_GROUP
-#define L8_TAP_GROUP 8  // pixels whose taps may be in flight together (8: no scheduling barrier)
-#endif
-// Production: occupancy 2 (two waves per SIMD hide each other's tap latency), which the accumulators in LDS and no
-// cross-group prefetch make fit in 256 registers without spills (244).  Measured (r03_b1): 2M points 1929 -> 1512 us
-// per launch (HBM frac 0.39 -> 0.50), 200k 243 -> 200 us, per-residual outputs bit-identical.
-#ifndef L8_MIN_WAVES
-#define L8_MIN_WAVES 2  // waves per SIMD the register budget must allow (launch bounds)
-#endif
-#ifndef L8_PREFETCH
-#define L8_PREFETCH 0   // 1: the next point group's inputs are loaded while the current group computes (occupancy 1)
-#endif
-#ifndef L8_FAST_OPS
-#define L8_FAST_OPS 7   // div_nr / sqrt_nr for: 1 the projection quotients, 2 the gradient weight, 4 the Huber weight
-#endif
-// Issue priority.  The two waves sharing a SIMD are VALU-bound together; with equal priority the arbiter's
-// oldest-first rule runs the older one ahead and leaves the younger alone on the SIMD at the end.  4 (production):
-// the pair takes turns, priority 1 on alternate groups.  Measured (r05_l6 / r05_l8, per launch, HBM roofline
-// fraction): 2M points 0.516 (4-wave blocks, no priority) -> 0.560 (8-wave blocks + turns); 200k 0.387 -> 0.378 ..
-// 0.388 (VALU-bound either way: the turns equalise the waves' end times, not the SIMD's work).
-// 0: none; 1: alternate per group (all waves in phase); 2: a wave ahead of the block's slowest yields.
-#ifndef L8_PRIO
-#define L8_PRIO 4
-#endif
-#ifndef L8_BOUNDS_BITS
-#define L8_BOUNDS_BITS 1  // the pixel bounds test on float bits (one unsigned range compare per coordinate)
-#endif
-#ifndef L8_TEXEL_BYTES
-#define L8_TEXEL_BYTES 12  // the taps' texel stride: 12 = the packed (I, dx, dy) copy, 16 = the float4 texels
-#endif
-#ifndef L8_BUFFER_TAPS
-#define L8_BUFFER_TAPS 1  // the pixel taps as buffer loads with 32-bit offsets (interp33_8b)
-#endif
-#ifndef L8_LDS_ACC
-#define L8_LDS_ACC 1    // the per-lane accumulators (T slice, accD / accE / accEB / accHcc) live in LDS between groups
-#endif
-#ifndef L8_PK_SC
-// the Schur accumulators' accD / accE updates as packed-fp32 pairs (v_pk_fma_f32) on operand pairs that are aligned
-// halves of the loaded JpJdF quads (no moves to form them); the same fmas, bit for bit.  Measured (per launch,
-// profiles/r06_mfma/valu_mfma_pk_ab.txt): 200k 151 -> 144 us, 2M 1324 -> 1254 us, 25k 38.2 -> 37.0 us.  (As one
-// product on v_mfma_f32_16x16x4_f32 they measured 137 / 1167 / 36.9 us; the path's specification keeps these small
-// accumulations off the matrix cores, so that form is kept out: tools/archive/r06_lin8_mfma_schur.diff)
-#define L8_PK_SC 1
-#endif
+// Occupancy 2 (two waves per SIMD hide each other's tap latency): the per-lane accumulators live in LDS between
+// point groups and a group's inputs are loaded when it starts, which fits 256 registers without spills (244).
+// Measured (r03_b1): 2M points 1929 -> 1512 us per launch (HBM frac 0.39 -> 0.50), 200k 243 -> 200 us, per-residual
+// outputs bit-identical.
+constexpr int MINW8 = 2;  // waves per SIMD the register budget must allow (launch bounds)
+constexpr int TB8 = 12;   // the taps' texel stride in bytes: the packed (I, dx, dy) copy of the images (a.img3)
 
 // Data (r, c), r <= c < 10, in the natural per-lane layout
 __host__ __device__ constexpr int didx(int r, int c) { return r * 10 - (r * (r - 1)) / 2 + (c - r); }
 constexpr int TR0 = 55, BR0 = 85;
 
-// getInterpolatedElement33 (Include/GlobalTypes.h:377-388) on float4 texels, through one buffer resource over every
-// frame's image: 32-bit texel offsets (one 24-bit multiply-add and one shift-add per pixel instead of 64-bit address
+// getInterpolatedElement33 (Include/GlobalTypes.h:377-388) on the packed texels, through one buffer resource over
+// every frame's image: 32-bit texel offsets (one 24-bit multiply-add and one shift-add per pixel instead of 64-bit address
 // arithmetic), the next row by the scalar offset, the x + 1 texel by the instruction offset; dx = fract(x), which is
 // x - (int)x exactly for the non-negative coordinates the caller passes
 __device__ __forceinline__ float3 ld_texel3(__amdgpu_buffer_rsrc_t r, int vo, int so) {
@@ -104,25 +66,13 @@ __device__ __forceinline__ float3 ld_texel3(__amdgpu_buffer_rsrc_t r, int vo, in
   return make_float3(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]));
 }
 __device__ __forceinline__ float3 interp33_8b(__amdgpu_buffer_rsrc_t img, int slot_b, float x, float y, int w) {
-  constexpr int TB = L8_TEXEL_BYTES;
+  constexpr int TB = TB8;
   const int ix = (int)x, iy = (int)y;
   const float dx = __builtin_amdgcn_fractf(x), dy = __builtin_amdgcn_fractf(y), dxdy = dx * dy;
   const int vo = __mul24(__mul24(iy, w) + ix, TB) + slot_b;
   const int row = __builtin_amdgcn_readfirstlane(w * TB);
   const float3 p00 = ld_texel3(img, vo, 0), p10 = ld_texel3(img, vo + TB, 0), p01 = ld_texel3(img, vo, row),
                p11 = ld_texel3(img, vo + TB, row);
-  const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-  float3 r;
-  r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
-  r.y = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
-  r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
-  return r;
-}
-__device__ __forceinline__ float3 interp33_8(const float4* __restrict__ img, float x, float y, int w) {
-  int ix = (int)x, iy = (int)y;
-  float dx = x - ix, dy = y - iy, dxdy = dx * dy;
-  const float4* bp = img + ix + iy * w;
-  const float4 p00 = bp[0], p10 = bp[1], p01 = bp[w], p11 = bp[w + 1];
   const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
   float3 r;
   r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
@@ -144,25 +94,10 @@ struct __align__(16) L8Scratch {
   float jb[8][8][8];  // [point][pattern row i][non-host slot o]: JpJdF (0 unless active), accD / accE operand
   float pp[8][8];     // [point][HdiF, bdSumF, Hcd0..3, -, -]
 };
-// the epilogue's per-wave partials: T (natural layout, summed over the wave's point lanes) and the D / E / C lanes
-struct __align__(16) L8Part {
-  float T[L8_NW][8][NTOP + 1];
-  float DEC[L8_NW][HS_ND_PROD + 6][64];
-};
-#if L8_LDS_ACC
-union __align__(16) L8Lds {
-  L8Scratch s[L8_NW];
-};
 // the per-lane accumulators in LDS, [wave][entry][lane] (lane-consecutive: conflict-free b32 accesses): T slice
 // entries 0..11 (lane (pl, t) holds entries 12 pl + i of slot t's natural layout), accD 12..39, accE / accEB 40..44,
 // accHcc / accbc 45
-constexpr int L8_NACC = 12 + HS_ND_PROD + 6;
-#else
-union __align__(16) L8Lds {
-  L8Scratch s[L8_NW];
-  L8Part part;
-};
-#endif
+constexpr int NACC8 = 12 + HS_ND_PROD + 6;
 
 // the owner of entry e of lane (t, k) in hs_k_lin's production layout, as an index of the natural T layout
 // (-1: the entry is never read by hs_k_reduce / hs_k_stitch)
@@ -273,8 +208,7 @@ __device__ __forceinline__ void slot_reduce_scatter(const TopOps& o, float (&out
   }
 }
 
-// a point group's inputs of one lane (point pl, target slot t), loaded one group ahead (software pipelining: the
-// next group's loads are in flight while the current group computes)
+// a point group's inputs of one lane (point pl, target slot t), loaded together when the group starts
 struct L8In {
   float idep, idep0, pu, pv;
   int res, st_raw;
@@ -312,13 +246,11 @@ __device__ __forceinline__ void l8_load(const HsLinArgs& a, int pc, int t, L8In&
 
 }  // namespace
 
-__global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs a) {
+__global__ __launch_bounds__(HS_LIN8_NT, MINW8) void hs_k_lin8(HsLinArgs a) {
   __shared__ L8Const K;
-  __shared__ L8Lds U;
+  __shared__ L8Scratch U[NW8];
   __shared__ unsigned int H1[HS_TH_BINS];  // the block's pass-1 histogram of its candidates (a.th_hist)
-#if L8_LDS_ACC
-  __shared__ float ACC[L8_NW][L8_NACC][64];
-#endif
+  __shared__ float ACC[NW8][NACC8][64];
   if (a.brk && a.st->stop) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int pl = lane >> 3, t = lane & 7;  // point of the group, target slot
@@ -359,46 +291,28 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
 
   const HsCalib cal = a.st->dcal;
   const HsLinParams lp = a.lp;
-  // div_nr / sqrt_nr in the pixel loop: the two thresholds bound its quotients' and roots' ranges (uniform)
-#if L8_BOUNDS_BITS
   // the pixel bounds 1.1 < PKu < W - 3, 1.1 < PKv < H - 3 (Src/OptimizationClasses.cpp:152) as unsigned spans of
   // float bits above 1.1f (an empty interval: span 0)
   constexpr unsigned kLo1 = 0x3f8ccccdu + 1u;  // __float_as_uint(1.1f) + 1
   const float wmax = (float)(cal.W - 3), hmax = (float)(cal.H - 3);
   const unsigned spanU = __builtin_amdgcn_readfirstlane(wmax > 1.1f ? __float_as_uint(wmax) - kLo1 : 0u);
   const unsigned spanV = __builtin_amdgcn_readfirstlane(hmax > 1.1f ? __float_as_uint(hmax) - kLo1 : 0u);
-#endif
+  // div_nr / sqrt_nr in the pixel loop: the two thresholds bound its quotients' and roots' ranges (uniform)
   const bool fast_ok = lp.outlierTHSumComponent >= 0x1p-30f && lp.outlierTHSumComponent <= 0x1p30f &&
                        lp.huberTH >= 0x1p-30f && lp.huberTH <= 0x1p30f;
   const int tc = t < nF ? t : 0;
-#if L8_BUFFER_TAPS
-  // every image slot through one resource (num_records: the whole 32-bit range; taps stay inside the slot's image):
-  // the packed 12-byte (I, dx, dy) copy (L8_TEXEL_BYTES 12) or the float4 texels (16)
-  const void* ibase = L8_TEXEL_BYTES == 12 ? (const void*)a.img3 : (const void*)a.img;
-  const __amdgpu_buffer_rsrc_t timg = __builtin_amdgcn_make_buffer_rsrc((void*)ibase, 0, 0x7fffffff, 0x00020000);
-  const int slot16 = hs_img_slot(a.img_slot, tc) * (int)a.img_stride * L8_TEXEL_BYTES;  // past the window: frame 0
-#else
-  const float4* timg = a.img + (long long)hs_img_slot(a.img_slot, tc) * a.img_stride;  // past the window: frame 0
-#endif
-  L8Scratch& W = U.s[wv];
+  // every image slot's packed 12-byte (I, dx, dy) texels through one resource (num_records: the whole 32-bit range;
+  // taps stay inside the slot's image)
+  const __amdgpu_buffer_rsrc_t timg = __builtin_amdgcn_make_buffer_rsrc((void*)a.img3, 0, 0x7fffffff, 0x00020000);
+  const int slot16 = hs_img_slot(a.img_slot, tc) * (int)a.img_stride * TB8;  // past the window: frame 0
+  L8Scratch& W = U[wv];
   const int oslot = t - (t > h ? 1 : 0);           // non-host slot index of t (t != h)
 
   // accumulators: T, the (host h, target t) block in natural layout, spread over the slot's 8 point lanes (lane (pl,
   // t) keeps entries 12 pl .. 12 pl + 11, summed per point group); D lane (row, col) = (pl, t), E lane (t, k) =
   // (pl, t) read as (slot pl, row t); C lanes 0..19
-#if L8_LDS_ACC
 #pragma unroll
-  for (int i = 0; i < L8_NACC; i++) ACC[wv][i][lane] = 0.f;
-#else
-  float Td[12];
-#pragma unroll
-  for (int i = 0; i < 12; i++) Td[i] = 0.f;
-  float D[HS_ND_PROD];
-#pragma unroll
-  for (int i = 0; i < HS_ND_PROD; i++) D[i] = 0.f;
-  float E[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  float C = 0.f;
-#endif
+  for (int i = 0; i < NACC8; i++) ACC[wv][i][lane] = 0.f;
   double eA = 0.0, sidA = 0.0, npA = 0.0;
 
   const int ngroups = (pe - pb + 7) >> 3;
@@ -406,41 +320,19 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
     const int pp = pb + g * 8 + pl;
     return pp < pe ? pp : (pe > pb ? pe - 1 : pb);
   };
-  L8In nx;  // the next group's inputs (loaded ahead; clamped addresses, so always valid)
-#if L8_PREFETCH
-  if (wv < ngroups) l8_load(a, clamp_p(wv), t, nx);
-#endif
-#if L8_PRIO == 2
-  __shared__ int l8_prog[L8_NW];
-  if (lane == 0) l8_prog[wv] = 0;
-  __syncthreads();
-#endif
+  L8In nx;  // the group's inputs (clamped addresses, so always valid)
   for (int gi = wv; gi < ngroups; gi += a.W) {  // wave-uniform
-#if L8_PRIO == 1
-    if (((gi - wv) / a.W) & 1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-#elif L8_PRIO == 4
-    // the two waves sharing a SIMD (wv, wv + 4: workgroup waves go round-robin over the 4 SIMDs) take turns
+    // Issue priority.  The two waves sharing a SIMD (wv, wv + 4: workgroup waves go round-robin over the 4 SIMDs)
+    // are VALU-bound together; with equal priority the arbiter's oldest-first rule runs the older one ahead and
+    // leaves the younger alone on the SIMD at the end.  So the pair takes turns: priority 1 on alternate groups.
+    // Measured (r05_l6 / r05_l8, per launch, HBM roofline fraction): 2M points 0.516 (4-wave blocks, no priority)
+    // -> 0.560 (8-wave blocks + turns); 200k 0.387 -> 0.378 .. 0.388 (VALU-bound either way: the turns equalise the
+    // waves' end times, not the SIMD's work).
+    static_assert(HS_LIN8_WAVES == 8, "the priority turns pair waves wv and wv + 4: two waves per SIMD");
     if ((((gi - wv) / a.W) + (wv >> 2)) & 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
-#elif L8_PRIO == 2
-    {  // the block's waves progress together: a wave ahead of the slowest one yields its issue priority
-      const int k = (gi - wv) / a.W;
-      if (lane == 0) l8_prog[wv] = k;
-      int mn = k;
-#pragma unroll
-      for (int w = 0; w < L8_NW; w++) mn = min(mn, l8_prog[w]);
-      if (__builtin_amdgcn_readfirstlane(mn) < k) __builtin_amdgcn_s_setprio(0);
-      else __builtin_amdgcn_s_setprio(2);
-    }
-#endif
-#if L8_PREFETCH
-    const L8In in = nx;
-    if (gi + a.W < ngroups) l8_load(a, clamp_p(gi + a.W), t, nx);  // in flight during this group's work
-#else
     l8_load(a, clamp_p(gi), t, nx);
     const L8In in = nx;
-#endif
     const int p = pb + gi * 8 + pl;
     const bool valid = p < pe;
     const int pc = valid ? p : pe - 1;
@@ -592,7 +484,7 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       q1 = q1 + pcr.Kt[1] * idep;
       q2 = q2 + pcr.Kt[2] * idep;
       float PKu, PKv;
-      if constexpr (FAST && (L8_FAST_OPS & 1)) {
+      if constexpr (FAST) {
         // |q2| in range: every in-bounds quotient is exact (out of bounds it stays out of bounds, or NaN)
         const unsigned aq2 = __float_as_uint(fabsf(q2));
         gq2max = max(gq2max, aq2);
@@ -606,18 +498,10 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       }
       // (the short-circuit form is a branch region per pixel, which keeps the scheduler from hoisting every pixel's
       // taps at once: the bitwise form spills)
-#if L8_BOUNDS_BITS
       // 1.1 < PK < W - 3 as one unsigned range test on the float bits (ordered like the values for positive floats;
       // negatives, -0 and NaN land above the range): the four compares' short-circuit form became 16-bit flag packing
       const bool okP = okC && (__float_as_uint(PKu) - kLo1 < spanU) && (__float_as_uint(PKv) - kLo1 < spanV);
-#else
-      const bool okP = okC && (PKu > 1.1f && PKv > 1.1f && PKu < (cal.W - 3) && PKv < (cal.H - 3));
-#endif
-#if L8_BUFFER_TAPS
       const float3 hit = interp33_8b(timg, slot16, okP ? PKu : 2.f, okP ? PKv : 2.f, cal.W);
-#else
-      const float3 hit = interp33_8(timg, okP ? PKu : 2.f, okP ? PKv : 2.f, cal.W);
-#endif
       const float color = colK[k];
       const float residual = hit.x - (float)(pcr.aff[0] * color + pcr.aff[1]);
       const float drdA = (color - pcr.b0);
@@ -627,13 +511,13 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       float w, hw;
       // the uniform thresholds are in [2^-30, 2^30] (checked by the caller): wden <= 2^60 and |residual| <= 2^60
       // keep both quotients and both square-root arguments in range (NaN operands fail the tests)
-      if constexpr (FAST && (L8_FAST_OPS & 2)) {
+      if constexpr (FAST) {
         gwmax = max(gwmax, __float_as_uint(wden));  // wden >= 0 (or NaN)
         w = sqrt_nr(div_nr(lp.outlierTHSumComponent, wden, rcp_nr(wden)));
       } else {
         w = sqrtf(lp.outlierTHSumComponent / wden);
       }
-      if constexpr (FAST && (L8_FAST_OPS & 4)) {
+      if constexpr (FAST) {
         grmax = max(grmax, __float_as_uint(fabsf(residual)));
         // == (|residual| < huberTH ? 1 : huberTH / |residual|): below the threshold the quotient rounds to >= 1 (or
         // is NaN for a zero / denormal divisor), and min returns 1 then; a NaN residual is flagged.  No select, so
@@ -645,7 +529,7 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       w = 0.5f * (w + wgtK[k]);
       float qv[Q8_N];
       qv[0] = w * w * hw * residual * residual * (2 - hw);
-      if constexpr (FAST && (L8_FAST_OPS & 4)) hw = sqrt_nr(hw);  // hw <= 1 and sqrt(1) == 1: == (hw < 1 ? sqrt(hw) : hw)
+      if constexpr (FAST) hw = sqrt_nr(hw);  // hw <= 1 and sqrt(1) == 1: == (hw < 1 ? sqrt(hw) : hw)
       else hw = hw < 1 ? sqrtf(hw) : hw;
       hw = hw * w;
       const float hy = hit.y * hw, hz = hit.z * hw;
@@ -673,9 +557,6 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       qv[16] = rz * rz;
 #pragma unroll
       for (int i = 0; i < Q8_N; i++) S[i] = S[i] + qv[i];
-      // the taps of at most L8_TAP_GROUP pixels in flight per wave (register budget of two waves per SIMD: the
-      // other wave hides the gather latency the compiler's full hoisting hid at one wave per SIMD)
-      if (L8_TAP_GROUP < 8 && (k + 1) % L8_TAP_GROUP == 0) __builtin_amdgcn_sched_barrier(0);
     }
     };
     {
@@ -818,13 +699,8 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       for (int i = 0; i < 6; i++) o.br[i] = active ? br[i] : 0.f;
       float red[12];
       slot_reduce_scatter(o, red, pl);
-#if L8_LDS_ACC
 #pragma unroll
       for (int i = 0; i < 12; i++) ACC[wv][i][lane] += red[i];
-#else
-#pragma unroll
-      for (int i = 0; i < 12; i++) Td[i] += red[i];
-#endif
     }
     // ---- Schur accumulators (Src/AccumulatedSCHessian.cpp:32-51) through the wave's scratch: accD (lane = (row,
     //      col) of every (o1 <= o2) block), accE / accEB (lane = (slot, row)), accHcc / accbc (lanes 0..19)
@@ -846,7 +722,12 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       const int eo = es - (es > h ? 1 : 0);
       const int cr = (lane >> 2) & 3, ccol = lane & 3;
       const unsigned long long wbits = actBits;
-#if L8_PK_SC
+      // accD / accE updates as packed-fp32 pairs (v_pk_fma_f32) on operand pairs that are aligned halves of the
+      // loaded JpJdF quads (no moves to form them); the same fmas as the scalar form, bit for bit.  Measured (per
+      // launch, profiles/r06_mfma/valu_mfma_pk_ab.txt): 200k 151 -> 144 us, 2M 1324 -> 1254 us, 25k 38.2 -> 37.0 us.
+      // (As one product on v_mfma_f32_16x16x4_f32 they measured 137 / 1167 / 36.9 us; the path's specification keeps
+      // these small accumulations off the matrix cores, so that form is kept out:
+      // tools/archive/r06_lin8_mfma_schur.diff)
       l8f2 DP[9];
       float DS[10];
 #pragma unroll
@@ -863,14 +744,6 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
 #pragma unroll
       for (int i = 0; i < 5; i++) E[i] = ACC[wv][12 + HS_ND_PROD + i][lane];
       C = ACC[wv][12 + HS_ND_PROD + 5][lane];
-#elif L8_LDS_ACC
-      float D[HS_ND_PROD], E[5], C;
-#pragma unroll
-      for (int i = 0; i < HS_ND_PROD; i++) D[i] = ACC[wv][12 + i][lane];
-#pragma unroll
-      for (int i = 0; i < 5; i++) E[i] = ACC[wv][12 + HS_ND_PROD + i][lane];
-      C = ACC[wv][12 + HS_ND_PROD + 5][lane];
-#endif
 #pragma unroll
       for (int qp = 0; qp < 8; qp++) {
         const unsigned mq = (unsigned)(wbits >> (qp * 8)) & 0xffu;  // uniform
@@ -878,14 +751,12 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
         const float4 pp0 = *reinterpret_cast<const float4*>(&W.pp[qp][0]);
         const float4 pp1 = *reinterpret_cast<const float4*>(&W.pp[qp][4]);
         const float hdf = pp0.x, bsf = pp0.y;
-        const float hcv[4] = {pp0.z, pp0.w, pp1.x, pp1.y};
         const float4 r0 = *reinterpret_cast<const float4*>(&W.jb[qp][dr][0]);
         const float4 r1 = *reinterpret_cast<const float4*>(&W.jb[qp][dr][4]);
         const float4 c0 = *reinterpret_cast<const float4*>(&W.jb[qp][dc][0]);
         const float4 c1 = *reinterpret_cast<const float4*>(&W.jb[qp][dc][4]);
         const float j1[7] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z};
         const float j2[7] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z};
-#if L8_PK_SC
         const l8f2 j2p[3] = {l8f2{c0.x, c0.y}, l8f2{c0.z, c0.w}, l8f2{c1.x, c1.y}};
 #pragma unroll
         for (int o1 = 0; o1 < 7; o1++) {
@@ -905,26 +776,9 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
           E[0] = e01.x; E[1] = e01.y; E[2] = e23.x; E[3] = e23.y;
           E[4] += (hdf * bsf) * jv;
         }
-#else
-#pragma unroll
-        for (int o1 = 0; o1 < 7; o1++) {
-          const float wl = hdf * j1[o1];
-#pragma unroll
-          for (int o2 = o1; o2 < 7; o2++) D[o1 * 7 - (o1 * (o1 - 1)) / 2 + (o2 - o1)] += wl * j2[o2];
-        }
-        {  // predicated, not branched: jb holds 0 for an inactive residual, and the host slot reads 0
-          const float jv = es != h ? W.jb[qp][ek][min(eo, 6)] : 0.f;
-          const float wl = hdf * jv;
-#pragma unroll
-          for (int c = 0; c < 4; c++) E[c] += wl * hcv[c];
-          E[4] += (hdf * bsf) * jv;
-        }
-#endif
         const float hr = W.pp[qp][2 + cr], hc = W.pp[qp][2 + ccol];  // per-lane LDS addresses, no select chains
         C += lane < 16 ? (hdf * hr) * hc : (bsf * hdf) * hc;
       }
-#if L8_LDS_ACC
-#if L8_PK_SC
 #pragma unroll
       for (int o1 = 0; o1 < 7; o1++)
 #pragma unroll
@@ -933,23 +787,16 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
           ACC[wv][12 + o1 * 7 - (o1 * (o1 - 1)) / 2 + (o2 - o1)][lane] =
               ds.kind == 1 ? DS[ds.idx] : ((o2 & 1) ? DP[ds.idx].y : DP[ds.idx].x);
         }
-#else
-#pragma unroll
-      for (int i = 0; i < HS_ND_PROD; i++) ACC[wv][12 + i][lane] = D[i];
-#endif
 #pragma unroll
       for (int i = 0; i < 5; i++) ACC[wv][12 + HS_ND_PROD + i][lane] = E[i];
       ACC[wv][12 + HS_ND_PROD + 5][lane] = C;
-#endif
     }
     __builtin_amdgcn_wave_barrier();  // the scratch is rewritten by the next group
     if (a.trace && tid == 0 && gi == wv) a.trace[(size_t)b * 16 + 12] = wall_clock64();  // wave 0's first group
   }
   if (a.trace && tid == 0) a.trace[(size_t)b * 16 + 1] = wall_clock64();
   if (a.trace && lane == 0 && wv < 8) a.trace[(size_t)b * 16 + 3 + wv] = wall_clock64();  // each wave's loop end
-#if L8_PRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
   if (!a.accumulate) return;
 
   // ---- epilogue: the block partial in hs_k_lin's production layout (T entries from their owner lanes), waves in
@@ -962,19 +809,8 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
     sW += __shfl(sidA, j * 8);
     nW += __shfl(npA, j * 8);
   }
-  __syncthreads();  // every wave is done with its scratch (the partials area aliases it)
-#if !L8_LDS_ACC
-  L8Part& P = U.part;
-#pragma unroll
-  for (int i = 0; i < 12; i++)
-    if (12 * pl + i < NTOP) P.T[wv][t][12 * pl + i] = Td[i];
-#pragma unroll
-  for (int i = 0; i < HS_ND_PROD; i++) P.DEC[wv][i][lane] = D[i];
-#pragma unroll
-  for (int i = 0; i < 5; i++) P.DEC[wv][HS_ND_PROD + i][lane] = E[i];
-  P.DEC[wv][HS_ND_PROD + 5][lane] = C;
-#endif
-  __shared__ double se[L8_NW][3];
+  __syncthreads();  // every wave's accumulators are complete in ACC
+  __shared__ double se[NW8][3];
   if (lane == 0) {
     se[wv][0] = eW;
     se[wv][1] = sW;
@@ -991,35 +827,23 @@ __global__ __launch_bounds__(HS_LIN8_NT, L8_MIN_WAVES) void hs_k_lin8(HsLinArgs 
       const int tt = l >> 3, kk = l & 7;
       const int m = owner_map(e, kk);
       if (m >= 0) {
-#if L8_LDS_ACC
         const int sl8 = (m / 12) * 8 + tt, si = m % 12;  // entry m of slot tt: lane (m / 12, tt), slice entry m % 12
         s = ACC[0][si][sl8];
 #pragma unroll
-        for (int w = 1; w < L8_NW; w++) s += ACC[w][si][sl8];
-#else
-        s = P.T[0][tt][m];
-#pragma unroll
-        for (int w = 1; w < L8_NW; w++) s += P.T[w][tt][m];
-#endif
+        for (int w = 1; w < NW8; w++) s += ACC[w][si][sl8];
       }
     } else {
       const int d = e - HS_E_TOP;
-#if L8_LDS_ACC
       s = ACC[0][12 + d][l];
 #pragma unroll
-      for (int w = 1; w < L8_NW; w++) s += ACC[w][12 + d][l];
-#else
-      s = P.DEC[0][d][l];
-#pragma unroll
-      for (int w = 1; w < L8_NW; w++) s += P.DEC[w][d][l];
-#endif
+      for (int w = 1; w < NW8; w++) s += ACC[w][12 + d][l];
     }
     out[i] = s;
   }
   if (tid < 3) {
     double s = se[0][tid];
 #pragma unroll
-    for (int w = 1; w < L8_NW; w++) s += se[w][tid];
+    for (int w = 1; w < NW8; w++) s += se[w][tid];
     a.part_e[(size_t)b * 4 + tid] = s;
   }
   if (a.th_hist)  // (every wave's candidates are in: the barriers above)

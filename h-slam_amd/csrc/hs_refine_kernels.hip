@@ -30,6 +30,7 @@
 
 #include <cfloat>
 
+#include "hs_interp.h"
 #include "hs_refine_kernels.h"
 
 namespace {
@@ -40,20 +41,9 @@ constexpr int NACC = 45;            // upper triangle of the 9x9 [J | r] system
 constexpr int NX = 12;              // per-lane values folded by the leader: e, maxstep, dp_j * dd (8), r * dd, dd * dd
 __constant__ int kPat[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
 
-__device__ __forceinline__ float3 ref_interp33(const float4* __restrict__ img, float x, float y, int w) {
-  int ix = (int)x, iy = (int)y;
-  float dx = x - ix, dy = y - iy, dxdy = dx * dy;
-  const float4* bp = img + ix + iy * w;
-  const float4 p00 = bp[0], p10 = bp[1], p01 = bp[w], p11 = bp[w + 1];
-  const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-  float3 r;
-  r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
-  r.y = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
-  r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
-  return r;
-}
 // getInterpolatedElement31 of the first frame; the base texel index is clamped to the buffer (the reference
-// reads outside it, undefined behaviour, exactly where the clamp acts)
+// reads outside it, undefined behaviour, exactly where the clamp acts).  hs_img::interp31 computes the same values
+// but compiles to other code here (a 32-bit base), so this copy stays.
 __device__ __forceinline__ float ref_interp31(const float4* __restrict__ img, float x, float y, int w, int h) {
   int ix = (int)x, iy = (int)y;
   float dx = x - ix, dy = y - iy, dxdy = dx * dy;
@@ -306,7 +296,7 @@ __device__ __forceinline__ bool ref_pixel(const HsRefArgs& a, const HsRefPass& S
   const float Kv = a.fy * v + a.cy;
   const float new_idepth = idn / pt[2];
   if (!(Ku > 1 && Kv > 1 && Ku < a.W - 2 && Kv < a.H - 2 && new_idepth > 0)) return false;
-  const float3 hit = ref_interp33(a.img2, Ku, Kv, a.W);
+  const float3 hit = hs_img::interp33_unclamped(a.img2, Ku, Kv, a.W);
   const float rlR = ref_interp31(a.img1, x, y, a.W, a.H);
   if (!isfinite(rlR) || !isfinite(hit.x)) return false;
   const float residual = hit.x - S.r2a * rlR - S.r2b;

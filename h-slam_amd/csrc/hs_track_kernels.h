@@ -85,8 +85,6 @@ constexpr int HS_TRK_MAXG = 16;
 constexpr int HS_TRK_MAXLVSEQ = 8;  // level ends per track (<= 5 levels + one repeated level)
 
 __global__ void hs_k_track(HsTrackArgs a);
-__global__ void hs_k_trk_scatter(int n, const float* cu, const float* cv, const float* cid, const float* hdi, int w,
-                                 int h, float* idepth0, float* wsum0);
 constexpr int HS_TRK_SCAT_CAP = 8192;  // points sorted in LDS by hs_k_trk_scatter_sorted (dynamic LDS: 8 B each)
 __global__ void hs_k_trk_scatter_sorted(const int* d_n, int n_arg, const float* cu, const float* cv, const float* cid,
                                         const float* hdi, int w, int h, float* idepth0, float* wsum0);

@@ -1,8 +1,9 @@
 // hs_track_kernels.hip — gfx950 kernels of H-SLAM's CoarseTracker.
 //
 //   makeCoarseDepthL0 (Src/CoarseTracker.cpp:105-263), once per keyframe:
-//     hs_k_trk_scatter      point -> level-0 idepth / weight sums, in the reference's point order (1 thread:
-//                           colliding points add in order, so the sums are the reference's)
+//     hs_k_trk_scatter_sorted
+//                           point -> level-0 idepth / weight sums, colliding points added in the reference's point
+//                           order (sorted by pixel in LDS; hs_k_trk_scatter_seq, one thread, beyond its capacity)
 //     hs_k_trk_down         2x2 sums up the pyramid
 //     hs_k_trk_dilate       one dilation pass (diagonal neighbours on levels 0-1, 4-neighbours above)
 //     hs_k_trk_count / hs_k_trk_scan / hs_k_trk_compact
@@ -21,6 +22,7 @@
 
 #include <cfloat>
 
+#include "hs_kernels.h"
 #include "hs_track_kernels.h"
 #include "hs_se3_dev.h"
 
@@ -28,30 +30,9 @@ namespace {
 
 constexpr int TRK_NT = 512;
 constexpr int TRK_B = 4;
-#ifndef TRK_MEET_F32
-#define TRK_MEET_F32 1  // member meetings exchange fp32 block totals (one granule per value) instead of fp64 (two)
-#endif              // points per thread whose loads are in flight together
 constexpr int TRK_NACC = 45;          // upper triangle of the 9x9 [J | r] normal equations
 constexpr int TRK_NRED = TRK_NACC + 4 + 3;  // + E, flowT, flowRT, flowNum | numE, numSat, numWarped
 static_assert(TRK_NRED == HS_TRK_NRED, "pass partial layout");
-
-__device__ __forceinline__ float3 interp33(const float4* __restrict__ img, float x, float y, int w) {
-  int ix = (int)x, iy = (int)y;
-  float dx = x - ix, dy = y - iy, dxdy = dx * dy;
-  const float4* bp = img + ix + iy * w;
-  const float4 p00 = bp[0], p10 = bp[1], p01 = bp[w], p11 = bp[w + 1];
-  const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-  float3 r;
-  r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
-  r.y = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
-  r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
-  return r;
-}
-
-#define HS_TRACE(A, slot)                                                                          \
-  do {                                                                                             \
-    if ((A).trace && threadIdx.x == 0) (A).trace[(size_t)blockIdx.x * 16 + (slot)] = wall_clock64(); \
-  } while (0)
 
 __device__ __forceinline__ double trk_readlane_f64(double v, int lane) {
   const long long b = __double_as_longlong(v);
@@ -322,7 +303,7 @@ __device__ void trk_pass(const HsTrackArgs& a, TrkShared& S, int h, int g, bool 
       Kv[b] = fyl * v[b] + cyl;
       new_idepth[b] = id[b] / pt2;
       inb[b] = i < n && (Ku[b] > 2 && Kv[b] > 2 && Ku[b] < wl - 3 && Kv[b] < hl - 3 && new_idepth[b] > 0);
-      // bilinear taps (interp33), requested for every point of the slot; out-of-bounds points read pixel 0
+      // bilinear taps (hs_img::interp33_unclamped's, hs_interp.h), requested for every point of the slot; out-of-bounds points read pixel 0
       const float sx = inb[b] ? Ku[b] : 0.f, sy = inb[b] ? Kv[b] : 0.f;
       const int ix = (int)sx, iy = (int)sy;
       fdx[b] = sx - ix;
@@ -455,24 +436,25 @@ __device__ void trk_pass(const HsTrackArgs& a, TrkShared& S, int h, int g, bool 
     const long long pt1 = (a.trace && lane == 0) ? clock64() + (long long)(tot * 0.0) : 0;
     if (G > 1) {
       // The hypothesis' workgroups meet by granules (cdna_hip_programming.md §6 Guideline 16, R2: the data is the
-      // flag): every fp64 partial goes out as two 8-byte {tag, 32-bit half} granules (sc1 stores), and lane q
-      // re-reads the 2 G granules of its value (sc1 loads) until every tag matches, then sums the G partials in
-      // workgroup order.  One memory round trip per poll, no counter, no fences.  The tag carries the launch's epoch
-      // and the pass, so granules left by earlier launches never match; the pass parity keeps a fast member off a
-      // slow member's buffer (it cannot write pass k + 2 before every member has read pass k).
+      // flag): every partial goes out as one 8-byte {tag, fp32 bits} granule (sc1 stores), and lane q re-reads the
+      // G granules of its value (sc1 loads) until every tag matches, then sums the G partials in workgroup order.
+      // One memory round trip per poll, no counter, no fences.  The tag carries the launch's epoch and the pass, so
+      // granules left by earlier launches never match; the pass parity keeps a fast member off a slow member's
+      // buffer (it cannot write pass k + 2 before every member has read pass k).
       typedef unsigned long long u64;
       u64* P = reinterpret_cast<u64*>(a.part) + ((size_t)h * 2 + (S.npass & 1)) * HS_TRK_MAXG * TRK_NRED * 2;
       const unsigned int tg = (a.epoch << HS_TRK_PASS_BITS) | (unsigned int)(S.npass + 1);
       const u64 tag = (u64)tg << 32;
-#if TRK_MEET_F32
-      // one granule per value: the member's block total rounded to fp32 (every consumer below reads the pass totals
-      // as fp32: H / b from (float) tot, the energies and counts as floats / small integers), summed over the
-      // members in fp64 in member order: half the stores and polled loads of the fp64 form
+      // the member's block total rounded to fp32 (every consumer below reads the pass totals as fp32: H / b from
+      // (float) tot, the energies and counts as floats / small integers), summed over the members in fp64 in member
+      // order: half the stores and polled loads of two granules per fp64 value
       if (lane < TRK_NRED)
         __hip_atomic_store(P + g * TRK_NRED + lane, tag | (u64)__float_as_uint((float)tot), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
       u64 v[HS_TRK_MAXG];
       const long long pm0 = (a.trace && lane == 0) ? clock64() : 0;
+      // the poll's time bound on the constant 100 MHz wall clock (spin_limit ticks, set by the host from the clock
+      // rate); after a timeout (S.dead) a meeting polls once
       const unsigned long long t_end = wall_clock64() + (S.dead ? 0ull : (unsigned long long)a.spin_limit);
       for (;;) {
 #pragma unroll
@@ -500,57 +482,6 @@ __device__ void trk_pass(const HsTrackArgs& a, TrkShared& S, int h, int g, bool 
       for (int gg = 0; gg < HS_TRK_MAXG; gg++)
         if (gg < G) tot += (double)__uint_as_float((unsigned int)(v[gg] & 0xffffffffull));
     }
-#else
-      if (lane < TRK_NRED) {
-        const u64 bits = (u64)__double_as_longlong(tot);
-        __hip_atomic_store(P + (g * TRK_NRED + lane) * 2, tag | (bits & 0xffffffffull), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(P + (g * TRK_NRED + lane) * 2 + 1, tag | (bits >> 32), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      }
-      u64 v[2 * HS_TRK_MAXG];
-      const long long pm0 = (a.trace && lane == 0) ? clock64() : 0;
-      // the poll's time bound on the constant 100 MHz wall clock (spin_limit ticks, set by the host from the clock
-      // rate); after a timeout (S.dead) a meeting polls once
-      const unsigned long long t_end = wall_clock64() + (S.dead ? 0ull : (unsigned long long)a.spin_limit);
-      for (;;) {
-        bool ok = true;
-#pragma unroll
-        for (int gg = 0; gg < HS_TRK_MAXG; gg++)
-          if (gg < G) {
-            v[2 * gg] = __hip_atomic_load(P + (gg * TRK_NRED + q) * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            v[2 * gg + 1] = __hip_atomic_load(P + (gg * TRK_NRED + q) * 2 + 1, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT);
-          }
-#pragma unroll
-        for (int gg = 0; gg < HS_TRK_MAXG; gg++)
-          if (gg < G) ok = ok && (unsigned int)(v[2 * gg] >> 32) == tg && (unsigned int)(v[2 * gg + 1] >> 32) == tg;
-        if (__all(ok)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (wall_clock64() >= t_end) {  // a member never arrived (not co-resident): flag the hypothesis, go on
-          if (lane == 0) {
-            __hip_atomic_store(a.cnt + h, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            S.dead = 1;
-          }
-          break;
-        }
-      }
-      if (a.trace && lane == 0) {
-        S.prof[8] += clock64() - pm0;  // the meeting: own stores to every member's granules seen
-        S.prof[9] += 1;
-      }
-      tot = 0.0;
-      if (G == HS_TRK_MAXG) {  // (uniform) the production member count: no per-slot masks
-#pragma unroll
-        for (int gg = 0; gg < HS_TRK_MAXG; gg++)
-          tot += __longlong_as_double((long long)((v[2 * gg] & 0xffffffffull) | (v[2 * gg + 1] << 32)));
-      } else {
-#pragma unroll
-        for (int gg = 0; gg < HS_TRK_MAXG; gg++)
-          if (gg < G) tot += __longlong_as_double((long long)((v[2 * gg] & 0xffffffffull) | (v[2 * gg + 1] << 32)));
-      }
-    }
-#endif
     const float Ef = (float)trk_readlane_f64(tot, TRK_NACC + 0);
     const float fT = (float)trk_readlane_f64(tot, TRK_NACC + 1), fRT = (float)trk_readlane_f64(tot, TRK_NACC + 2);
     const float fN = (float)trk_readlane_f64(tot, TRK_NACC + 3);
@@ -987,12 +918,6 @@ __device__ void hs_k_trk_scatter_seq(int n, const float* cu, const float* cv, co
     idepth0[u + w * v] += new_idepth * weight;
     wsum0[u + w * v] += weight;
   }
-}
-
-__global__ void hs_k_trk_scatter(int n, const float* cu, const float* cv, const float* cid, const float* hdi, int w,
-                                 int h, float* idepth0, float* wsum0) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  hs_k_trk_scatter_seq(n, cu, cv, cid, hdi, w, h, idepth0, wsum0);
 }
 
 // makeCoarseDepthL0's point loop in parallel with the sequential loop's sums: the points are sorted by (pixel,
