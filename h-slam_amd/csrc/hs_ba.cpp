@@ -215,6 +215,8 @@ int ensure_capacity(hs_ctx* c, int W, int H, int capP, int capBlk) {
   c->h_stage_cap = c->d_stage_cap = stage_bytes(capP);
   HS_TRY(c->cap.pinned(&c->h_stage, c->h_stage_cap));
   HS_TRY(dalloc(&c->d_stage, c->d_stage_cap));
+  HS_TRY(dalloc(&c->d_act_stage, capP));
+  c->n_dev_staged = 0;
   HS_TRY(c->cap.pinned(&c->h_raw, npx));
   HS_TRY(dalloc(&c->d_raw, npx));
   const char* tr = std::getenv("HS_KTRACE");
@@ -1193,6 +1195,7 @@ int hs_ba_set_window(hs_ctx* c, const hs_camera* cam, int nF, const hs_frame* fr
   c->wframes.clear();
   c->wpts.clear();
   c->staged.clear();
+  c->n_dev_staged = 0;
   c->nF = nF;
   c->nP = nP;
   c->nR = nR;

@@ -142,6 +142,11 @@ struct hs_ctx : hs::Device {
   size_t h_stage_cap = 0;
   uint8_t* d_stage = nullptr;                     // its device copy
   size_t d_stage_cap = 0;
+  // points staged on the device since the last commit (hs_tracer_activate_ba): [cap_P] records, the first
+  // n_dev_staged in use; a WinPoint names entry k as src = -(1 + (k | HS_WIN_SRC_DEV))
+  HsStagedPoint* d_act_stage = nullptr;
+  int n_dev_staged = 0;
+  unsigned commit_seq = 0;                        // commits so far (hs_tracer_get_act_inputs: is the layout still the one read?)
 
   // ---- device
   float* d_img3 = nullptr;        // the same slots packed as (I, dI/dx, dI/dy) triplets: hs_k_lin8's taps (pack_slot)
@@ -293,6 +298,12 @@ int marginalize_frame_prior(hs_ctx* c, int frame, std::vector<double>& HMn, std:
 // the marginalization pass over the points flagged in d_marg (any: at least one is): HM / bM updated on the device
 int marginalize_flagged(hs_ctx* c, bool any);
 int commit(hs_ctx* c);            // hs_ba_window.cpp: apply pending structural edits (no-op when clean)
+// hs_ba_window.cpp: the mirror's part of an activation (optimizeImmaturePoint's new MapPoints): n points staged on the
+// device at d_act_stage[n_dev_staged ...], point k hosted on window frame host[k] with an IN residual into every
+// frame whose bit is set in res_in[k] (ascending), lastResiduals as hs_ba_insert_residuals sets them.  Validates
+// before it changes anything; handles_out (nullable) receives the new handles.
+int stage_activated(hs_ctx* c, int n, const int* host, const uint8_t* res_in, int* handles_out);
+int mirror_points(hs_ctx* c);     // points the mirror holds (committed and staged)
 inline int commit_if_dirty(hs_ctx* c) { return c->dirty ? commit(c) : HS_OK; }
 int max_blocks_for(int capP);
 // everything enqueued on the context's stream has finished: hipStreamSynchronize on a single-rank context; on a

@@ -85,6 +85,7 @@ void mirror_from_committed(hs_ctx* c) {
   }
   c->next_handle = maxh + 1;
   c->staged.clear();
+  c->n_dev_staged = 0;
   c->incremental = true;
 }
 
@@ -279,6 +280,7 @@ int commit(hs_ctx* c) {
   a.src = (const int*)dptr(src);
   a.newres = dptr(nres);
   a.staged = (const HsStagedPoint*)dptr(stg);
+  a.staged_dev = c->d_act_stage;
   const PointSet& F = c->ps[c->cur];
   const PointSet& T = c->ps[c->cur ^ 1];
   a.from = {F.u, F.v, F.idepth, F.idepth_zero, F.priorF, F.color, F.weight, F.relBL, F.nGood, F.r_state, F.r_center,
@@ -309,6 +311,8 @@ int commit(hs_ctx* c) {
   c->d_p_HdiF = hdif_dst;
   c->hdif_solved = hdif_dst;
   c->staged.clear();
+  c->n_dev_staged = 0;
+  c->commit_seq++;
   c->nP = nP;
   c->nR = r;
   c->cand_stride = c->cap_stride;
@@ -340,7 +344,7 @@ int hs_ba_reserve(hs_ctx* c, const hs_camera* cam, int max_points) {
   c->pt_host.clear(); c->pt_handle.clear(); c->res_point.clear(); c->res_target.clear();
   c->res_of_slot.clear(); c->res_order.clear();
   c->nblk = 0;
-  c->wframes.clear(); c->wpts.clear(); c->staged.clear(); c->loc_key.clear(); c->loc_idx.clear();
+  c->wframes.clear(); c->wpts.clear(); c->staged.clear(); c->n_dev_staged = 0; c->loc_key.clear(); c->loc_idx.clear();
   c->next_handle = 0;
   c->next_frame_key = 0;
   c->incremental = true;
@@ -467,11 +471,22 @@ int hs_ba_set_frame_image_device(hs_ctx* c, int frame, const void* d_texels) {
   return HS_OK;
 }
 
+// the mirror's half of hs_ba_insert_points / hs_ba_insert_residuals (no device work: hs_debug_act_mirror runs them on a
+// context without a device)
+static int mirror_insert_points(hs_ctx* c, const hs_points* pts, const float* relBL, const int* nGood,
+                                int* handles_out);
+static int mirror_insert_residuals(hs_ctx* c, int n, const int* handles, const int* targets, const uint8_t* states);
+
 int hs_ba_insert_points(hs_ctx* c, const hs_points* pts, const float* relBL, const int* nGood, int* handles_out) {
   if (!pts || pts->n < 0 || (pts->n > 0 && (!pts->host || !pts->u || !pts->v || !pts->idepth || !pts->idepth_zero ||
                                            !pts->color || !pts->weights)))
     return fail(HS_ERR_INVALID, "bad points");
   HS_TRY(ensure_incremental(c));
+  return mirror_insert_points(c, pts, relBL, nGood, handles_out);
+}
+
+static int mirror_insert_points(hs_ctx* c, const hs_points* pts, const float* relBL, const int* nGood,
+                                int* handles_out) {
   const int nF = (int)c->wframes.size();
   for (int i = 0; i < pts->n; i++)
     if (pts->host[i] < 0 || pts->host[i] >= nF) return fail(HS_ERR_INVALID, "bad point host");
@@ -522,6 +537,10 @@ static int add_residual(hs_ctx* c, WinPoint* w, int host_key, int t, uint8_t st)
 int hs_ba_insert_residuals(hs_ctx* c, int n, const int* handles, const int* targets, const uint8_t* states) {
   if (n < 0 || (n > 0 && (!handles || !targets))) return fail(HS_ERR_INVALID, "bad residual list");
   HS_TRY(ensure_incremental(c));
+  return mirror_insert_residuals(c, n, handles, targets, states);
+}
+
+static int mirror_insert_residuals(hs_ctx* c, int n, const int* handles, const int* targets, const uint8_t* states) {
   for (int i = 0; i < n; i++) {
     WinPoint* w = find_point(c, handles[i]);
     const uint8_t st = states ? states[i] : (uint8_t)HS_RES_IN;
@@ -876,7 +895,107 @@ int hs_ba_flag_points_for_removal(hs_ctx* c, int n_marg_frames, const int* marg_
 
 }  // extern "C"
 
+namespace hs {
+
+int mirror_points(hs_ctx* c) {
+  int n = 0;
+  for (auto& l : c->wpts) n += (int)l.size();
+  return n;
+}
+
+// optimizeImmaturePoint's new MapPoints (Src/FullSystemOptPoint.cpp:142-169) and their insertPoint / insertResidual
+// (Src/Mapping.cpp:440-455) in the mirror; the values lie in d_act_stage
+int stage_activated(hs_ctx* c, int n, const int* host, const uint8_t* res_in, int* handles_out) {
+  const int nF = (int)c->wframes.size();
+  if (n < 0 || (n > 0 && (!host || !res_in))) return fail(HS_ERR_INVALID, "bad activated list");
+  for (int k = 0; k < n; k++) {
+    if (host[k] < 0 || host[k] >= nF) return fail(HS_ERR_INVALID, "activated point on no window frame");
+    if ((res_in[k] >> host[k]) & 1u) return fail(HS_ERR_INVALID, "activated point with a residual into its host");
+    if (nF < 8 && (res_in[k] >> nF)) return fail(HS_ERR_INVALID, "activated point with a residual into no frame");
+  }
+  if (mirror_points(c) + n > c->cap_P || c->n_dev_staged + n > c->cap_P)
+    return fail(HS_ERR_NOMEM, "activated points exceed the reserved point capacity (hs_ba_reserve)");
+  for (int k = 0; k < n; k++) {
+    WinPoint w;
+    w.handle = c->next_handle++;
+    w.src = -(1 + ((c->n_dev_staged + k) | HS_WIN_SRC_DEV));
+    const int f = host[k], key = c->wframes[f].key;
+    for (int t = 0; t < nF; t++) {
+      if (!((res_in[k] >> t) & 1u)) continue;
+      HS_TRY(add_residual(c, &w, key, t, (uint8_t)HS_RES_IN));
+      const int s = nF - 1 - t;  // lastResiduals: an IN residual into the newest / second-newest frame
+      if (s == 0 || s == 1) {
+        w.last_key[s] = c->wframes[t].key;
+        w.last_code[s] = (uint8_t)HS_RES_IN;
+      }
+    }
+    set_loc(c, w.handle, key, (int)c->wpts[f].size());
+    c->wpts[f].push_back(w);
+    if (handles_out) handles_out[k] = w.handle;
+  }
+  c->n_dev_staged += n;
+  if (n > 0) c->dirty = true;
+  return HS_OK;
+}
+
+}  // namespace hs
+
+// test hook (not in the header, no device work): the mirror rule of hs::stage_activated (out_a) beside
+// hs_ba_insert_points + hs_ba_insert_residuals' (out_b) on two bare mirrors of nF frames, for n points hosted on
+// host[k] with the IN masks res_in[k].  Per point 12 ints: nres, the residual list's 7 target frames (-1 padded),
+// lastResiduals' two frames (-1: none) and two codes.
+extern "C" int hs_debug_act_mirror(int nF, int n, const int* host, const uint8_t* res_in, int* out_a, int* out_b) {
+  if (nF < 1 || nF > HS_MAXF || n < 0 || !host || !res_in || !out_a || !out_b) return fail(HS_ERR_INVALID, "bad argument");
+  int rc = HS_OK;
+  for (int path = 0; path < 2 && rc == HS_OK; path++) {
+    hs_ctx* c = new hs_ctx();
+    c->cap_P = std::max(n, 1);
+    c->incremental = true;
+    for (int f = 0; f < nF; f++) {
+      WinFrame w;
+      w.key = c->next_frame_key++;
+      w.slot = f;
+      c->wframes.push_back(w);
+      c->wpts.emplace_back();
+    }
+    std::vector<int> handles(std::max(n, 1));
+    if (path == 0) {
+      rc = stage_activated(c, n, host, res_in, handles.data());
+    } else {
+      const std::vector<float> z((size_t)std::max(n, 1) * 8, 0.f);
+      hs_points pts{};
+      pts.n = n;
+      pts.host = host;
+      pts.u = pts.v = pts.idepth = pts.idepth_zero = pts.color = pts.weights = z.data();
+      rc = mirror_insert_points(c, &pts, nullptr, nullptr, handles.data());
+      std::vector<int> hd, tg;
+      for (int k = 0; k < n; k++)
+        for (int t = 0; t < nF; t++)
+          if ((res_in[k] >> t) & 1u) {
+            hd.push_back(handles[k]);
+            tg.push_back(t);
+          }
+      if (rc == HS_OK) rc = mirror_insert_residuals(c, (int)hd.size(), hd.data(), tg.data(), nullptr);
+    }
+    int* out = path == 0 ? out_a : out_b;
+    for (int k = 0; k < n && rc == HS_OK; k++) {
+      const WinPoint* w = find_point(c, handles[k]);
+      int* o = out + (size_t)k * 12;
+      o[0] = w->nres;
+      for (int q = 0; q < 7; q++) o[1 + q] = q < w->nres ? frame_index(c, w->tgt[q]) : -1;
+      for (int s = 0; s < 2; s++) {
+        o[8 + s] = w->last_key[s] >= 0 ? frame_index(c, w->last_key[s]) : -1;
+        o[10 + s] = w->last_code[s];
+      }
+    }
+    delete c;
+  }
+  return rc;
+}
+
 // ---------------------------------------------------------------- test hooks (not part of include/hs_ba.h)
+// structural commits so far: each launches hs_k_win_gather once (tools/act_handoff_time.py counts a keyframe's)
+extern "C" int hs_debug_commit_count(hs_ctx* c) { return c ? (int)c->commit_seq : -1; }
 // The device window state (HsDevState: frames, calib, loop state) as a blob: tests/test_gpu_window.py transplants
 // it into a context rebuilt with hs_ba_set_window, so both run from the same fp64 frame state; setting it re-runs
 // setAdjointsF / setPrecalcValues / the projector on it, as a commit does.

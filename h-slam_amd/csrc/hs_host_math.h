@@ -193,6 +193,52 @@ HS_HD inline HsPrecalc make_precalc(const FrameH& H, const FrameH& T, const Cali
   return pc;
 }
 
+// ---- activatePointsMT's per-frame and per-pair inputs (hs_act_frame / hs_act_pair, include/hs_trace.h), written once
+// for the device (hs_k_act_form, hs_act_ba_kernels.hip) and the host (hs_debug_act_inputs).  Every product is a
+// left-to-right three-term sum (mm3f / mv3f) without contraction, so both sides round alike.
+//
+// CoarseDistanceMap::makeK (Src/CoarseTracker.cpp:870-899): K[1] and Ki[0] in float; fx[1] = fx[0] * 0.5 and
+// cx[1] = (cx[0] + 0.5) / 2 - 0.5 are double expressions rounded to float
+HS_HD inline void make_act_K(const CalibH& cal, float K1[9], float Ki0[9]) {
+#pragma clang fp contract(off)
+  const float fx0 = cal.value_scaledf[0], fy0 = cal.value_scaledf[1], cx0 = cal.value_scaledf[2],
+              cy0 = cal.value_scaledf[3];
+  const float K0[9] = {fx0, 0, cx0, 0, fy0, cy0, 0, 0, 1};
+  inv3f(K0, Ki0);
+  const float fx1 = (float)((double)fx0 * 0.5), fy1 = (float)((double)fy0 * 0.5);
+  const float cx1 = (float)(((double)cx0 + 0.5) / 2 - 0.5), cy1 = (float)(((double)cy0 + 0.5) / 2 - 0.5);
+  const float k1[9] = {fx1, 0, cx1, 0, fy1, cy1, 0, 0, 1};
+  for (int i = 0; i < 9; i++) K1[i] = k1[i];
+}
+// fhToNew = PRE_worldToCam[newest] * PRE_camToWorld[f]; K[1] * R.cast<float>() * Ki[0], K[1] * t.cast<float>()
+// (Src/Mapping.cpp:366-369, Src/CoarseTracker.cpp:742-744)
+HS_HD inline void make_act_frame(const FrameH& F, const FrameH& N, const float K1[9], const float Ki0[9],
+                                 float KRKi[9], float Kt[3]) {
+#pragma clang fp contract(off)
+  const SE3 fhToNew = N.PRE_worldToCam * F.PRE_camToWorld;
+  double R[9];
+  fhToNew.rotationMatrix(R);
+  float Rf[9], tf[3], KR[9];
+  for (int i = 0; i < 9; i++) Rf[i] = (float)R[i];
+  for (int i = 0; i < 3; i++) tf[i] = (float)fhToNew.t[i];
+  mm3f(K1, Rf, KR);
+  mm3f(KR, Ki0, KRKi);
+  mv3f(K1, tf, Kt);
+}
+// FrameFramePrecalc::set's PRE_RTll / PRE_tTll / PRE_aff_mode of (host H, target T)
+HS_HD inline void make_act_pair(const FrameH& H, const FrameH& T, float RTll[9], float tTll[3], float aff[2]) {
+#pragma clang fp contract(off)
+  const SE3 l2l = T.PRE_worldToCam * H.PRE_camToWorld;
+  double R[9];
+  l2l.rotationMatrix(R);
+  for (int i = 0; i < 9; i++) RTll[i] = (float)R[i];
+  for (int i = 0; i < 3; i++) tTll[i] = (float)l2l.t[i];
+  double a[2];
+  fromToVecExposure(H.ab_exposure, T.ab_exposure, H.aff_a(), H.aff_b(), T.aff_a(), T.aff_b(), a);
+  aff[0] = (float)a[0];
+  aff[1] = (float)a[1];
+}
+
 // setAdjointsF for one (h, t): AH, AT (row-major 8x8, fp64) + float copies
 HS_HD inline void make_adjoints(const FrameH& H, const FrameH& T, double AH[64], double AT[64]) {
   SE3 h2t = T.evalPT * H.evalPT.inverse();

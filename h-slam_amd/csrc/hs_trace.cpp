@@ -12,6 +12,7 @@
 
 #include "../../include/hs_ba.h"
 #include "../../include/hs_trace.h"
+#include "hs_ba_ctx.h"
 #include "hs_host.h"
 #include "hs_trace_kernels.h"
 #include "hs_pyr_kernels.h"
@@ -59,7 +60,29 @@ struct hs_tracer : hs::Device {
   float *d_frac = nullptr, *d_thr = nullptr, *d_act_idepth = nullptr;
   int* d_ap_frame = nullptr;
   float *d_ap_u = nullptr, *d_ap_v = nullptr, *d_ap_id = nullptr;
+  // host mirror of d_host (a point's image slot): the BA hand-off names each activated point's window frame, and the
+  // device compaction its survivors, without reading the slots back
+  std::vector<int> h_host;
+  // activation into a BA window and the device compaction (allocated by their first call)
+  bool ba_ready = false;
+  hipEvent_t ev_handoff = nullptr;      // tracer -> BA stream order (the staged points)
+  uint8_t* h_act_rb = nullptr;          // pinned read-back: toOptimize [cap] ints | action [cap] | IN masks [cap]
+  int* d_stage_pos = nullptr;           // hs_k_act_stage's ranks
+  HsCmpPointSet alt{};                  // the compaction's second buffer set (swapped with the live one)
+  int *d_cmp_pos = nullptr, *d_cmp_blk = nullptr;
+  uint8_t *d_cmp_keep = nullptr, *d_cmp_drop = nullptr;
+  bool action_valid = false;            // h_act_rb / d_action hold the last hs_tracer_activate_ba's actions of these points
+  // what the last hs_tracer_activate_ba formed and read (hs_tracer_get_act_inputs)
+  hs_ctx* in_ba = nullptr;
+  unsigned in_seq = 0;
+  int in_nF = 0, in_n_active = 0;
+  float in_K4[4] = {0, 0, 0, 0};
 };
+
+static HsCmpPointSet live_set(hs_tracer* t) {
+  return {t->d_host, t->d_u, t->d_v, t->d_color, t->d_weights, t->d_gradH, t->d_energyTH, t->d_quality, t->d_idmin,
+          t->d_idmax, t->d_uv, t->d_interval, t->d_status, t->d_steps, t->d_type};
+}
 
 static int upload_img(hs_tracer* t, float4* dst, const float* src) {
   const size_t n = (size_t)t->W * t->H;
@@ -158,6 +181,7 @@ void hs_tracer_destroy(hs_tracer* t) {
   (void)hipSetDevice(t->device);
   if (t->stream) (void)hipStreamSynchronize(t->stream);
   t->pool.release_all();
+  if (t->ev_handoff) (void)hipEventDestroy(t->ev_handoff);
   t->close();
   delete t;
 }
@@ -178,6 +202,8 @@ int hs_tracer_clear(hs_tracer* t) {
   if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
   t->n = 0;
   t->max_host = -1;
+  t->h_host.clear();
+  t->action_valid = false;
   return HS_OK;
 }
 
@@ -202,6 +228,8 @@ int hs_tracer_add_points(hs_tracer* t, int n, const int* host, const float* u, c
   for (int i = 0; i < n; i++) t->max_host = std::max(t->max_host, host[i]);
   HS_TRY(launch_ctor(t, f, n));
   HS_HIP(hipStreamSynchronize(t->stream));  // host arrays may go away after return
+  t->h_host.insert(t->h_host.end(), host, host + n);
+  t->action_valid = false;
   t->n += n;
   return HS_OK;
 }
@@ -230,6 +258,8 @@ int hs_tracer_add_keys(hs_tracer* t, hs_extractor* e, int slot, int* n_added) {
   HS_HIP(hipMemsetD32Async((hipDeviceptr_t)(t->d_type + f), 0x3f800000, n, t->stream));  // my_type 1.f
   t->max_host = std::max(t->max_host, slot);
   HS_TRY(launch_ctor(t, f, n));
+  t->h_host.insert(t->h_host.end(), (size_t)n, slot);
+  t->action_valid = false;
   t->n += n;
   return HS_OK;
 }
@@ -442,71 +472,42 @@ static void update_min_act_dist(const hs_params& P, int nPoints, float& d) {
   if (d > 4) d = 4;
 }
 
-int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_frame* frames, const hs_act_pair* pairs,
-                       int n_active, const int* act_frame, const float* act_u, const float* act_v,
-                       const float* act_idepth, int ef_nPoints, float* currentMinActDist, int n_order,
-                       const int* order, uint8_t* action, float* idepth, uint8_t* res_in, int* activated,
-                       int* n_activated) {
-  if (!t || !K4 || !frames || !pairs || !currentMinActDist) return hs::fail(HS_ERR_INVALID, "null argument");
-  if (nF < 2 || nF > HS_MAXF_ACT) return hs::fail(HS_ERR_INVALID, "window size out of range (2..8 keyframes)");
-  if (n_active < 0 || (n_active > 0 && (!act_frame || !act_u || !act_v || !act_idepth)))
-    return hs::fail(HS_ERR_INVALID, "bad active point arrays");
-  if (!(K4[0] > 0) || !(K4[1] > 0)) return hs::fail(HS_ERR_INVALID, "bad intrinsics");
-  std::vector<int> fos(HS_TRC_MAXHOST, -1);
-  for (int f = 0; f < nF; f++) {
-    const int sl = frames[f].slot;
-    if (sl < 0 || sl >= HS_TRC_MAXHOST || !t->d_host_img[sl]) return hs::fail(HS_ERR_INVALID, "window frame without an image slot");
-    if (fos[sl] >= 0) return hs::fail(HS_ERR_INVALID, "two window frames on one slot");
-    fos[sl] = f;
-  }
-  for (int i = 0; i < n_active; i++)
-    if (act_frame[i] < 0 || act_frame[i] >= nF) return hs::fail(HS_ERR_INVALID, "active point on no window frame");
-  const int m = order ? n_order : t->n;
-  if (order) {
-    if (n_order < 0 || n_order > t->n) return hs::fail(HS_ERR_INVALID, "bad n_order");
-    std::vector<char> seen(t->n, 0);
-    for (int j = 0; j < n_order; j++) {
-      if (order[j] < 0 || order[j] >= t->n || seen[order[j]]) return hs::fail(HS_ERR_INVALID, "order is not a subset permutation");
-      seen[order[j]] = 1;
-    }
-  }
-  HS_HIP(hipSetDevice(t->device));
-  HS_TRY(sync_stats(t));
-  HS_TRY(act_alloc(t));
-  HS_TRY(act_points_alloc(t, std::max(1, n_active)));
-  update_min_act_dist(t->P, ef_nPoints, *currentMinActDist);
+// the kernels of one activatePointsMT call: seed, cand, dist, select, dist, optimize.  The frames / pairs / slot
+// table / order are on the device already; the active points are read where r says (the tracer's own upload, or a BA
+// context's point set).  Synchronises once, for the candidate count.
+struct ActRun {
+  const float* K4;
+  int nF, n_active;
+  const int* d_frame;
+  const float *d_u, *d_v, *d_idepth;
+  int m;            // loop-order entries
+  bool has_order;   // t->d_order holds them (else storage order)
+  float cmad;       // currentMinActDist after its update
+};
+
+static int act_launch(hs_tracer* t, const ActRun& r, int* n_toopt_out) {
   hipStream_t s = t->stream;
-  const int wh1 = t->w1 * t->h1;
-  HS_HIP(hipMemcpyAsync(t->d_act_frames, frames, sizeof(hs_act_frame) * nF, hipMemcpyHostToDevice, s));
-  HS_HIP(hipMemcpyAsync(t->d_act_pairs, pairs, sizeof(hs_act_pair) * nF * nF, hipMemcpyHostToDevice, s));
-  HS_HIP(hipMemcpyAsync(t->d_frame_of_slot, fos.data(), sizeof(int) * HS_TRC_MAXHOST, hipMemcpyHostToDevice, s));
-  if (order && m > 0) HS_HIP(hipMemcpyAsync(t->d_order, order, sizeof(int) * m, hipMemcpyHostToDevice, s));
-  if (n_active > 0) {
-    HS_HIP(hipMemcpyAsync(t->d_ap_frame, act_frame, sizeof(int) * n_active, hipMemcpyHostToDevice, s));
-    HS_HIP(hipMemcpyAsync(t->d_ap_u, act_u, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
-    HS_HIP(hipMemcpyAsync(t->d_ap_v, act_v, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
-    HS_HIP(hipMemcpyAsync(t->d_ap_id, act_idepth, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
-  }
+  const int wh1 = t->w1 * t->h1, nF = r.nF, m = r.m;
   HS_HIP(hipMemsetAsync(t->d_dist, 0xff, (wh1 + 3) & ~3, s));
   HS_HIP(hipMemsetAsync(t->d_act_cnt, 0, sizeof(int) * 2, s));
   HS_HIP(hipMemsetAsync(t->d_action, HS_ACT_KEEP, std::max(1, t->n), s));
   HS_HIP(hipMemsetAsync(t->d_res_in, 0, std::max(1, t->n), s));
 
   HsActSeedArgs sa;
-  sa.n = n_active;
+  sa.n = r.n_active;
   sa.newest = nF - 1;
   sa.w1 = t->w1;
   sa.h1 = t->h1;
   sa.frames = t->d_act_frames;
-  sa.frame = t->d_ap_frame;
-  sa.u = t->d_ap_u;
-  sa.v = t->d_ap_v;
-  sa.idepth = t->d_ap_id;
+  sa.frame = r.d_frame;
+  sa.u = r.d_u;
+  sa.v = r.d_v;
+  sa.idepth = r.d_idepth;
   sa.dist = t->d_dist;
   sa.list = t->d_list_a;
   sa.count = t->d_act_cnt;
-  if (n_active > 0) {
-    hipLaunchKernelGGL(hs_k_act_seed, dim3((n_active + 255) / 256), dim3(256), 0, s, sa);
+  if (r.n_active > 0) {
+    hipLaunchKernelGGL(hs_k_act_seed, dim3((r.n_active + 255) / 256), dim3(256), 0, s, sa);
     HS_HIP(hipGetLastError());
   }
   HsActCandArgs ca;
@@ -515,8 +516,8 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   ca.w1 = t->w1;
   ca.h1 = t->h1;
   ca.minTraceQuality = t->P.minTraceQuality;
-  ca.currentMinActDist = *currentMinActDist;
-  ca.order = order ? t->d_order : nullptr;
+  ca.currentMinActDist = r.cmad;
+  ca.order = r.has_order ? t->d_order : nullptr;
   ca.frame_of_slot = t->d_frame_of_slot;
   ca.frames = t->d_act_frames;
   ca.host = t->d_host;
@@ -560,7 +561,7 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
   se.h1 = t->h1;
   const size_t map_bytes = (size_t)((wh1 + 3) & ~3);
   se.lds_map = map_bytes <= HS_ACT_LDS_MAP_MAX ? 1 : 0;
-  se.order = order ? t->d_order : nullptr;
+  se.order = r.has_order ? t->d_order : nullptr;
   se.cand = t->d_cand;
   se.cell = t->d_cell;
   se.frac = t->d_frac;
@@ -608,12 +609,12 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
     oa.nF = nF;
     oa.W = t->W;
     oa.H = t->H;
-    oa.fxl = K4[0];
-    oa.fyl = K4[1];
-    oa.cxl = K4[2];
-    oa.cyl = K4[3];
-    oa.fxli = 1.0f / K4[0];
-    oa.fyli = 1.0f / K4[1];
+    oa.fxl = r.K4[0];
+    oa.fyl = r.K4[1];
+    oa.cxl = r.K4[2];
+    oa.cyl = r.K4[3];
+    oa.fxli = 1.0f / r.K4[0];
+    oa.fyli = 1.0f / r.K4[1];
     oa.huberTH = t->P.huberTH;
     oa.minIdepthH_act = t->P.minIdepthH_act;
     oa.GNIts = t->P.GNItsOnPointActivation;
@@ -636,6 +637,59 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
     hipLaunchKernelGGL(hs_k_act_optimize, dim3((n_toopt + 3) / 4), dim3(256), 0, s, oa);
     HS_HIP(hipGetLastError());
   }
+  *n_toopt_out = n_toopt;
+  return HS_OK;
+}
+
+int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_frame* frames, const hs_act_pair* pairs,
+                       int n_active, const int* act_frame, const float* act_u, const float* act_v,
+                       const float* act_idepth, int ef_nPoints, float* currentMinActDist, int n_order,
+                       const int* order, uint8_t* action, float* idepth, uint8_t* res_in, int* activated,
+                       int* n_activated) {
+  if (!t || !K4 || !frames || !pairs || !currentMinActDist) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (nF < 2 || nF > HS_MAXF_ACT) return hs::fail(HS_ERR_INVALID, "window size out of range (2..8 keyframes)");
+  if (n_active < 0 || (n_active > 0 && (!act_frame || !act_u || !act_v || !act_idepth)))
+    return hs::fail(HS_ERR_INVALID, "bad active point arrays");
+  if (!(K4[0] > 0) || !(K4[1] > 0)) return hs::fail(HS_ERR_INVALID, "bad intrinsics");
+  std::vector<int> fos(HS_TRC_MAXHOST, -1);
+  for (int f = 0; f < nF; f++) {
+    const int sl = frames[f].slot;
+    if (sl < 0 || sl >= HS_TRC_MAXHOST || !t->d_host_img[sl]) return hs::fail(HS_ERR_INVALID, "window frame without an image slot");
+    if (fos[sl] >= 0) return hs::fail(HS_ERR_INVALID, "two window frames on one slot");
+    fos[sl] = f;
+  }
+  for (int i = 0; i < n_active; i++)
+    if (act_frame[i] < 0 || act_frame[i] >= nF) return hs::fail(HS_ERR_INVALID, "active point on no window frame");
+  const int m = order ? n_order : t->n;
+  if (order) {
+    if (n_order < 0 || n_order > t->n) return hs::fail(HS_ERR_INVALID, "bad n_order");
+    std::vector<char> seen(t->n, 0);
+    for (int j = 0; j < n_order; j++) {
+      if (order[j] < 0 || order[j] >= t->n || seen[order[j]]) return hs::fail(HS_ERR_INVALID, "order is not a subset permutation");
+      seen[order[j]] = 1;
+    }
+  }
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(sync_stats(t));
+  HS_TRY(act_alloc(t));
+  HS_TRY(act_points_alloc(t, std::max(1, n_active)));
+  update_min_act_dist(t->P, ef_nPoints, *currentMinActDist);
+  t->action_valid = false;
+  hipStream_t s = t->stream;
+  HS_HIP(hipMemcpyAsync(t->d_act_frames, frames, sizeof(hs_act_frame) * nF, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(t->d_act_pairs, pairs, sizeof(hs_act_pair) * nF * nF, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(t->d_frame_of_slot, fos.data(), sizeof(int) * HS_TRC_MAXHOST, hipMemcpyHostToDevice, s));
+  if (order && m > 0) HS_HIP(hipMemcpyAsync(t->d_order, order, sizeof(int) * m, hipMemcpyHostToDevice, s));
+  if (n_active > 0) {
+    HS_HIP(hipMemcpyAsync(t->d_ap_frame, act_frame, sizeof(int) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_u, act_u, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_v, act_v, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
+    HS_HIP(hipMemcpyAsync(t->d_ap_id, act_idepth, sizeof(float) * n_active, hipMemcpyHostToDevice, s));
+  }
+  int n_toopt = 0;
+  const ActRun run{K4, nF, n_active, t->d_ap_frame, t->d_ap_u, t->d_ap_v, t->d_ap_id, m, order != nullptr,
+                   *currentMinActDist};
+  HS_TRY(act_launch(t, run, &n_toopt));
   const size_t n = t->n;
   std::vector<uint8_t> act(std::max<size_t>(1, n));
   std::vector<int> toopt(std::max(1, n_toopt));
@@ -712,7 +766,313 @@ int hs_tracer_compact(hs_tracer* t, const uint8_t* keep) {
   if (!idx.empty()) HS_HIP(hipMemcpy(hosts.data(), t->d_host, sizeof(int) * idx.size(), hipMemcpyDeviceToHost));
   t->max_host = -1;
   for (int h : hosts) t->max_host = std::max(t->max_host, h);
+  t->h_host.swap(hosts);
+  t->action_valid = false;
   t->n = (int)idx.size();
+  return HS_OK;
+}
+
+// ---- activation into a BA window, compaction on the device ------------------------------------------------------
+
+static int act_ba_alloc(hs_tracer* t) {
+  if (t->ba_ready) return HS_OK;
+  const size_t c = t->cap;
+  hs::Pool& m = t->pool;
+  if (!t->ev_handoff) HS_HIP(hipEventCreateWithFlags(&t->ev_handoff, hipEventDisableTiming));
+  HS_TRY(m.pinned(&t->h_act_rb, 6 * c));
+  HS_TRY(m.alloc(&t->d_stage_pos, c));
+  HsCmpPointSet& a = t->alt;
+  HS_TRY(m.alloc(&a.host, c));
+  HS_TRY(m.alloc(&a.u, c));
+  HS_TRY(m.alloc(&a.v, c));
+  HS_TRY(m.alloc(&a.color, 8 * c));
+  HS_TRY(m.alloc(&a.weights, 8 * c));
+  HS_TRY(m.alloc(&a.gradH, 4 * c));
+  HS_TRY(m.alloc(&a.energyTH, c));
+  HS_TRY(m.alloc(&a.quality, c));
+  HS_TRY(m.alloc(&a.idmin, c));
+  HS_TRY(m.alloc(&a.idmax, c));
+  HS_TRY(m.alloc(&a.uv, 2 * c));
+  HS_TRY(m.alloc(&a.interval, c));
+  HS_TRY(m.alloc(&a.status, c));
+  HS_TRY(m.alloc(&a.steps, c));
+  HS_TRY(m.alloc(&a.type, c));
+  HS_TRY(m.alloc(&t->d_cmp_pos, c));
+  HS_TRY(m.alloc(&t->d_cmp_blk, (c + HS_CMP_NT - 1) / HS_CMP_NT));
+  HS_TRY(m.alloc(&t->d_cmp_keep, c));
+  HS_TRY(m.alloc(&t->d_cmp_drop, HS_TRC_MAXHOST));
+  t->ba_ready = true;
+  return HS_OK;
+}
+
+// keep (host flags, one per point; null: the last hs_tracer_activate_ba's action == HS_ACT_KEEP) and not
+// drop_slot[slot]: the survivors into the second buffer set in their order, then the sets swap.  No read-back: the
+// host decides the same flags from its mirror of the points' slots.
+static int compact_on_device(hs_tracer* t, const uint8_t* keep, const uint8_t* drop_slot) {
+  const int n = t->n;
+  const uint8_t* act = t->h_act_rb + 4 * (size_t)t->cap;
+  std::vector<int> hosts;
+  hosts.reserve(n);
+  for (int i = 0; i < n; i++) {
+    const int h = t->h_host[i];
+    const bool k = (keep ? keep[i] != 0 : act[i] == HS_ACT_KEEP) && !(drop_slot && drop_slot[h]);
+    if (k) hosts.push_back(h);
+  }
+  if (n > 0) {
+    hipStream_t s = t->stream;
+    HsCmpArgs a;
+    a.n = n;
+    a.keep_in = nullptr;
+    if (keep) {
+      HS_HIP(hipMemcpyAsync(t->d_cmp_keep, keep, n, hipMemcpyHostToDevice, s));
+      a.keep_in = t->d_cmp_keep;
+    }
+    a.action = t->d_action;
+    a.drop_slot = nullptr;
+    if (drop_slot) {
+      HS_HIP(hipMemcpyAsync(t->d_cmp_drop, drop_slot, HS_TRC_MAXHOST, hipMemcpyHostToDevice, s));
+      a.drop_slot = t->d_cmp_drop;
+    }
+    a.pos = t->d_cmp_pos;
+    a.blk = t->d_cmp_blk;
+    a.from = live_set(t);
+    a.to = t->alt;
+    const int nblk = (n + HS_CMP_NT - 1) / HS_CMP_NT;
+    hipLaunchKernelGGL(hs_k_cmp_flags, dim3(nblk), dim3(HS_CMP_NT), 0, s, a);
+    HS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hs_k_cmp_scan, dim3(1), dim3(1024), 0, s, a, nblk);
+    HS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hs_k_cmp_scatter, dim3((int)(((size_t)n * 8 + 255) / 256)), dim3(256), 0, s, a);
+    HS_HIP(hipGetLastError());
+    if (keep || drop_slot) HS_HIP(hipStreamSynchronize(s));  // the caller's flag arrays may go away after return
+    HsCmpPointSet& b = t->alt;
+    std::swap(t->d_host, b.host);
+    std::swap(t->d_u, b.u);
+    std::swap(t->d_v, b.v);
+    std::swap(t->d_color, b.color);
+    std::swap(t->d_weights, b.weights);
+    std::swap(t->d_gradH, b.gradH);
+    std::swap(t->d_energyTH, b.energyTH);
+    std::swap(t->d_quality, b.quality);
+    std::swap(t->d_idmin, b.idmin);
+    std::swap(t->d_idmax, b.idmax);
+    std::swap(t->d_uv, b.uv);
+    std::swap(t->d_interval, b.interval);
+    std::swap(t->d_status, b.status);
+    std::swap(t->d_steps, b.steps);
+    std::swap(t->d_type, b.type);
+  }
+  t->max_host = -1;
+  for (int h : hosts) t->max_host = std::max(t->max_host, h);
+  t->h_host.swap(hosts);
+  t->n = (int)t->h_host.size();
+  t->action_valid = false;
+  return HS_OK;
+}
+
+int hs_tracer_compact_device(hs_tracer* t, const uint8_t* keep, const uint8_t* drop_slot, int* n_left) {
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
+  if (!keep && t->n > 0 && !t->action_valid)
+    return hs::fail(HS_ERR_STATE, "no keep flags and no hs_tracer_activate_ba actions of these points");
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(sync_stats(t));
+  HS_TRY(act_alloc(t));
+  HS_TRY(act_ba_alloc(t));
+  HS_TRY(compact_on_device(t, keep, drop_slot));
+  if (n_left) *n_left = t->n;
+  return HS_OK;
+}
+
+int hs_tracer_activate_ba(hs_tracer* t, hs_ctx* ba, int nF, const int* slots, const int* flagged_for_marg,
+                          float* currentMinActDist, int n_order, const int* order, int compact,
+                          const uint8_t* drop_slot, uint8_t* action_out, int* handles_out, int* n_activated,
+                          int* n_deleted) {
+  if (!t || !ba || !slots || !flagged_for_marg || !currentMinActDist) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (ba->comm_lost) return hs::fail(HS_ERR_RCCL, "communicator aborted by an earlier call (a peer rank failed)");
+  if (ba->multi_rank()) return hs::fail(HS_ERR_STATE, "hs_tracer_activate_ba needs a single-rank BA context");
+  if (ba->device != t->device) return hs::fail(HS_ERR_INVALID, "tracer and BA context on different devices");
+  if (!ba->d_state || !ba->haveCam) return hs::fail(HS_ERR_STATE, "the BA context has no window");
+  if (ba->cam.width != t->W || ba->cam.height != t->H) return hs::fail(HS_ERR_INVALID, "image size mismatch");
+  const int wnF = ba->incremental ? (int)ba->wframes.size() : ba->nF;
+  if (nF < 2 || nF > HS_MAXF_ACT) return hs::fail(HS_ERR_INVALID, "window size out of range (2..8 keyframes)");
+  if (nF != wnF) return hs::fail(HS_ERR_INVALID, "nF differs from the BA window's number of frames");
+  std::vector<int> fos(HS_TRC_MAXHOST, -1);
+  for (int f = 0; f < nF; f++) {
+    const int sl = slots[f];
+    if (sl < 0 || sl >= HS_TRC_MAXHOST || !t->d_host_img[sl])
+      return hs::fail(HS_ERR_INVALID, "window frame without an image slot");
+    if (fos[sl] >= 0) return hs::fail(HS_ERR_INVALID, "two window frames on one slot");
+    fos[sl] = f;
+  }
+  const int m = order ? n_order : t->n;
+  if (order) {
+    if (n_order < 0 || n_order > t->n) return hs::fail(HS_ERR_INVALID, "bad n_order");
+    std::vector<char> seen(t->n, 0);
+    for (int j = 0; j < n_order; j++) {
+      if (order[j] < 0 || order[j] >= t->n || seen[order[j]])
+        return hs::fail(HS_ERR_INVALID, "order is not a subset permutation");
+      seen[order[j]] = 1;
+    }
+  }
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(sync_stats(t));
+  HS_TRY(act_alloc(t));
+  HS_TRY(act_ba_alloc(t));
+  // The newest frame (and whatever else is pending: the last keyframe's removals) becomes visible on the device: the
+  // pending edits are committed first; the points activated here are committed by the caller's makeIDX.
+  HS_TRY(hs_ba_make_idx(ba, nullptr, nullptr, nullptr));
+  if (!ba->h_state_valid) HS_TRY(hs::fetch_state(ba));  // the calibration (a commit with a new frame left it valid)
+  float K4[4];
+  for (int k = 0; k < 4; k++) K4[k] = ba->h_state->calib.value_scaledf[k];
+  if (!(K4[0] > 0) || !(K4[1] > 0)) return hs::fail(HS_ERR_STATE, "bad intrinsics in the BA context");
+  const int n_active = ba->nP;
+  float cmad = *currentMinActDist;
+  update_min_act_dist(t->P, n_active, cmad);
+  hipStream_t s = t->stream;
+  // the tracer's stream after the BA's: the committed point set and the frames' state
+  HS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
+  HS_HIP(hipStreamWaitEvent(s, ba->ev_ready, 0));
+  HsActFormArgs fa;
+  fa.nF = nF;
+  for (int f = 0; f < 8; f++) {
+    fa.slot[f] = f < nF ? slots[f] : -1;
+    fa.flagged[f] = f < nF ? flagged_for_marg[f] : 0;
+  }
+  fa.st = ba->d_state;
+  fa.frames = t->d_act_frames;
+  fa.pairs = t->d_act_pairs;
+  hipLaunchKernelGGL(hs_k_act_form, dim3(1), dim3(64), 0, s, fa);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(t->d_frame_of_slot, fos.data(), sizeof(int) * HS_TRC_MAXHOST, hipMemcpyHostToDevice, s));
+  if (order && m > 0) HS_HIP(hipMemcpyAsync(t->d_order, order, sizeof(int) * m, hipMemcpyHostToDevice, s));
+  t->in_ba = ba;
+  t->in_seq = ba->commit_seq;
+  t->in_nF = nF;
+  t->in_n_active = n_active;
+  memcpy(t->in_K4, K4, sizeof(K4));
+  t->action_valid = false;
+  int n_toopt = 0;
+  const ActRun run{K4, nF, n_active, ba->d_pt_host, ba->d_u, ba->d_v, ba->d_idepth, m, order != nullptr, cmad};
+  HS_TRY(act_launch(t, run, &n_toopt));
+  // the structural read-back: actions, IN masks, the toOptimize list (pinned, one sync)
+  const size_t n = t->n, cap = t->cap;
+  int* h_toopt = reinterpret_cast<int*>(t->h_act_rb);
+  uint8_t* h_action = t->h_act_rb + 4 * cap;
+  uint8_t* h_res_in = t->h_act_rb + 5 * cap;
+  if (n) {
+    HS_HIP(hipMemcpyAsync(h_action, t->d_action, n, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipMemcpyAsync(h_res_in, t->d_res_in, n, hipMemcpyDeviceToHost, s));
+  }
+  if (n_toopt > 0) HS_HIP(hipMemcpyAsync(h_toopt, t->d_toopt, sizeof(int) * n_toopt, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  std::vector<int> host_frame;
+  std::vector<uint8_t> masks;
+  for (int k = 0; k < n_toopt; k++) {
+    const int i = h_toopt[k];
+    if (h_action[i] != HS_ACT_ACTIVATED) continue;
+    host_frame.push_back(fos[t->h_host[i]]);
+    masks.push_back(h_res_in[i]);
+  }
+  const int na = (int)host_frame.size();
+  if (hs::mirror_points(ba) + na > ba->cap_P || ba->n_dev_staged + na > ba->cap_P)
+    return hs::fail(HS_ERR_NOMEM, "activated points exceed the BA context's point capacity (hs_ba_reserve)");
+  const int base = ba->n_dev_staged;
+  HS_TRY(hs::stage_activated(ba, na, host_frame.data(), masks.data(), handles_out));
+  if (na > 0) {
+    HsActStageArgs sa;
+    sa.n = n_toopt;
+    sa.base = base;
+    sa.toopt = t->d_toopt;
+    sa.action = t->d_action;
+    sa.idepth = t->d_act_idepth;
+    sa.u = t->d_u;
+    sa.v = t->d_v;
+    sa.color = t->d_color;
+    sa.weights = t->d_weights;
+    sa.pos = t->d_stage_pos;
+    sa.out = ba->d_act_stage;
+    hipLaunchKernelGGL(hs_k_act_stage, dim3(1), dim3(1024), 0, s, sa);
+    HS_HIP(hipGetLastError());
+    // the BA's commit gathers the staged points: its stream after the tracer's
+    HS_HIP(hipEventRecord(t->ev_handoff, s));
+    HS_HIP(hipStreamWaitEvent(ba->stream, t->ev_handoff, 0));
+  }
+  *currentMinActDist = cmad;
+  if (action_out && n) memcpy(action_out, h_action, n);
+  int nd = 0;
+  for (size_t i = 0; i < n; i++) nd += h_action[i] == HS_ACT_DELETED;
+  if (n_activated) *n_activated = na;
+  if (n_deleted) *n_deleted = nd;
+  t->action_valid = true;
+  if (compact) HS_TRY(compact_on_device(t, nullptr, drop_slot));
+  return HS_OK;
+}
+
+int hs_tracer_get_act_inputs(hs_tracer* t, hs_ctx* ba, float K4[4], int* nF, hs_act_frame* frames, hs_act_pair* pairs,
+                             int* n_active, int* act_frame, float* act_u, float* act_v, float* act_idepth) {
+  if (!t || !ba) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (t->in_ba != ba || !t->in_nF) return hs::fail(HS_ERR_STATE, "no hs_tracer_activate_ba with this BA context");
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipStreamSynchronize(t->stream));
+  if (K4) memcpy(K4, t->in_K4, sizeof(t->in_K4));
+  if (nF) *nF = t->in_nF;
+  if (n_active) *n_active = t->in_n_active;
+  const int f = t->in_nF;
+  if (frames) HS_HIP(hipMemcpy(frames, t->d_act_frames, sizeof(hs_act_frame) * f, hipMemcpyDeviceToHost));
+  if (pairs) HS_HIP(hipMemcpy(pairs, t->d_act_pairs, sizeof(hs_act_pair) * f * f, hipMemcpyDeviceToHost));
+  if (act_frame || act_u || act_v || act_idepth) {
+    // the active points were read where they lie in the BA's point set: gone with its next commit
+    if (ba->commit_seq != t->in_seq)
+      return hs::fail(HS_ERR_STATE, "the BA window was committed since the activation: its point arrays moved");
+    const size_t n = t->in_n_active;
+    HS_TRY(hs::wait_stream(ba));
+    if (n && act_frame) HS_HIP(hipMemcpy(act_frame, ba->d_pt_host, 4 * n, hipMemcpyDeviceToHost));
+    if (n && act_u) HS_HIP(hipMemcpy(act_u, ba->d_u, 4 * n, hipMemcpyDeviceToHost));
+    if (n && act_v) HS_HIP(hipMemcpy(act_v, ba->d_v, 4 * n, hipMemcpyDeviceToHost));
+    if (n && act_idepth) HS_HIP(hipMemcpy(act_idepth, ba->d_idepth, 4 * n, hipMemcpyDeviceToHost));
+  }
+  return HS_OK;
+}
+
+// test hook (not in the header, no device work): hs_host_math.h's make_act_* on the host -- the inlines
+// hs_k_act_form runs.  The frames come from a device-state blob (hs_debug_get_state), or, with state == NULL, from
+// nF poses: worldToCam [nF][7] (SE3 data, taken as PRE_worldToCam), aff [nF][2] (aff_g2l a, b), exposure [nF] and the
+// level-0 K4.  Out: frames [nF] (slot / flag 0), pairs [nF*nF], kk [18] = K[1] | Ki[0].
+int hs_debug_act_inputs(const void* state, int nF, const double* worldToCam, const double* aff, const float* exposure,
+                        const float* K4, hs_act_frame* frames, hs_act_pair* pairs, float* kk) {
+  if (nF < 1 || nF > HS_MAXF || !frames || !pairs) return hs::fail(HS_ERR_INVALID, "bad argument");
+  std::vector<hs::FrameH> fr(nF);
+  hs::CalibH cal;
+  if (state) {
+    const HsDevState* S = static_cast<const HsDevState*>(state);
+    for (int f = 0; f < nF; f++) fr[f] = S->frames[f];
+    cal = S->calib;
+  } else {
+    if (!worldToCam || !aff || !exposure || !K4) return hs::fail(HS_ERR_INVALID, "bad argument");
+    for (int f = 0; f < nF; f++) {
+      fr[f].PRE_worldToCam = hs::SE3::fromData(worldToCam + 7 * f);
+      fr[f].PRE_camToWorld = fr[f].PRE_worldToCam.inverse();
+      fr[f].state_scaled[6] = aff[2 * f];
+      fr[f].state_scaled[7] = aff[2 * f + 1];
+      fr[f].ab_exposure = exposure[f];
+    }
+    for (int k = 0; k < 4; k++) cal.value_scaledf[k] = K4[k];
+  }
+  float K1[9], Ki0[9];
+  hs::make_act_K(cal, K1, Ki0);
+  if (kk) {
+    memcpy(kk, K1, sizeof(K1));
+    memcpy(kk + 9, Ki0, sizeof(Ki0));
+  }
+  for (int h = 0; h < nF; h++) {
+    frames[h].slot = 0;
+    frames[h].flagged_for_marg = 0;
+    hs::make_act_frame(fr[h], fr[nF - 1], K1, Ki0, frames[h].KRKi, frames[h].Kt);
+    for (int t = 0; t < nF; t++) {
+      hs_act_pair& p = pairs[h * nF + t];
+      hs::make_act_pair(fr[h], fr[t], p.RTll, p.tTll, p.aff);
+    }
+  }
   return HS_OK;
 }
 

@@ -148,6 +148,60 @@ struct HsActOptArgs {
   uint8_t* res_in;
 };
 
+// ---- activation into the BA window (hs_tracer_activate_ba), hs_act_ba_kernels.hip ---------------------------
+struct HsDevState;
+struct HsStagedPoint;
+
+// the window's hs_act_frame / hs_act_pair records from the BA context's device state (hs_host_math.h make_act_*)
+struct HsActFormArgs {
+  int nF;
+  int slot[8], flagged[8];   // per window frame: tracer image slot, FlaggedForMarginalization
+  const HsDevState* st;
+  hs_act_frame* frames;      // [nF]
+  hs_act_pair* pairs;        // [nF*nF] host*nF + target
+};
+
+// one HsStagedPoint per activated point, in toOptimize order, into the BA context's staging array
+struct HsActStageArgs {
+  int n;                     // toOptimize entries
+  int base;                  // first free entry of `out`
+  const int* toopt;
+  const uint8_t* action;
+  const float* idepth;       // the optimised idepth, per tracer point
+  const float* u;
+  const float* v;
+  const float* color;        // [points][8]
+  const float* weights;
+  int* pos;                  // [n] scratch: rank of the entry among the activated ones, -1 = not activated
+  HsStagedPoint* out;
+};
+
+// stable compaction of the tracer's points: keep flags, a two-level exclusive scan, a scatter into the second
+// buffer set.  keep = (keep_in ? keep_in[i] != 0 : action[i] == HS_ACT_KEEP) and not drop_slot[host[i]].
+constexpr int HS_CMP_NT = 1024;
+struct HsCmpPointSet {
+  int* host;
+  float *u, *v, *color, *weights, *gradH, *energyTH, *quality, *idmin, *idmax, *uv, *interval;
+  uint8_t* status;
+  int* steps;
+  float* type;
+};
+struct HsCmpArgs {
+  int n;
+  const uint8_t* keep_in;    // nullable
+  const uint8_t* action;     // read when keep_in is null
+  const uint8_t* drop_slot;  // nullable, [HS_TRC_MAXHOST]
+  int* pos;                  // [n] position inside the point's block, -1 = dropped
+  int* blk;                  // [blocks] kept per block, then (hs_k_cmp_scan) their exclusive prefix
+  HsCmpPointSet from, to;
+};
+
+__global__ void hs_k_act_form(HsActFormArgs a);
+__global__ void hs_k_act_stage(HsActStageArgs a);
+__global__ void hs_k_cmp_flags(HsCmpArgs a);
+__global__ void hs_k_cmp_scan(HsCmpArgs a, int nblk);
+__global__ void hs_k_cmp_scatter(HsCmpArgs a);
+
 __global__ void hs_k_act_seed(HsActSeedArgs a);
 __global__ void hs_k_act_cand(HsActCandArgs a);
 __global__ void hs_k_act_dist(HsActDistArgs a);

@@ -16,7 +16,11 @@ constexpr unsigned HS_WIN_NONE = 0xFE;  // no residual in this slot
 // is the window frame whose residual state the optimize tail copies into the slot, (int8) -1 when that residual is gone
 constexpr unsigned HS_WIN_LAST_KEEP = 0x10;
 
-// a point inserted since the last commit (uploaded with the commit's structure)
+// a staged point's src is -(1 + k); k carries this bit when the point lies in the context's device staging array
+// (written by hs_tracer_activate_ba's hs_k_act_stage) and not in the commit blob
+constexpr int HS_WIN_SRC_DEV = 1 << 30;
+
+// a point inserted since the last commit (uploaded with the commit's structure, or staged on the device)
 struct HsStagedPoint {
   float u, v, idepth, idepth_zero, priorF, relBL;
   int nGood;
@@ -36,9 +40,10 @@ struct HsWinGatherArgs {
   int nF;                       // frames of the new layout
   int col_src[HS_MAXF];         // new frame column -> old column (-1: inserted since the last commit)
   float th_init[HS_MAXF];       // frameEnergyTH of the inserted frames
-  const int* src;               // [n] old position, or -(1 + k) for staged point k
+  const int* src;               // [n] old position, or -(1 + k) for staged point k (k | HS_WIN_SRC_DEV: of staged_dev)
   const uint8_t* newres;        // [n][8] slot codes
   const HsStagedPoint* staged;
+  const HsStagedPoint* staged_dev;  // the context's device staging array (hs_ctx::d_act_stage)
   HsWinPointSet from, to;
   const float* hdif_from;       // the last solve's HdiF (old layout)
   float* hdif_to;

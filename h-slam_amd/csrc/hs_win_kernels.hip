@@ -42,7 +42,9 @@ __global__ __launch_bounds__(256) void hs_k_win_gather(HsWinGatherArgs a) {
       a.hdif_to[p] = a.hdif_from[src];
     }
   } else {
-    const HsStagedPoint& s = a.staged[-src - 1];
+    // a staged point: the commit blob's (hs_ba_insert_points), or the device staging array hs_k_act_stage filled
+    const int k = -src - 1;
+    const HsStagedPoint& s = (k & HS_WIN_SRC_DEV) ? a.staged_dev[k & ~HS_WIN_SRC_DEV] : a.staged[k];
     a.to.color[o] = s.color[t];
     a.to.weight[o] = s.weight[t];
     if (t == 0) {

@@ -158,6 +158,13 @@ SIGNATURES = {
     "hs_tracer_activate": ([VP, VP, I, VP, VP, I, VP, VP, VP, VP, I, VP, I, VP, VP, VP, VP, VP, VP], I),
     "hs_tracer_get_distance_map": ([VP, VP], I),
     "hs_tracer_compact": ([VP, VP], I),
+    "hs_tracer_activate_ba": ([VP, VP, I, VP, VP, VP, I, VP, I, VP, VP, VP, VP, VP], I),
+    "hs_tracer_compact_device": ([VP, VP, VP, VP], I),
+    "hs_tracer_get_act_inputs": ([VP] * 11, I),
+    # test hooks (not in the header, no device work): the formed activation inputs and the mirror rule on the host
+    "hs_debug_act_inputs": ([VP, I, VP, VP, VP, VP, VP, VP, VP], I),
+    "hs_debug_act_mirror": ([I, I, VP, VP, VP, VP], I),
+    "hs_debug_commit_count": ([VP], I),
     "hs_tracer_set_frame": ([VP, VP], I),
     "hs_tracer_set_frame_raw": ([VP, VP], I),
     "hs_tracer_trace": ([VP, I, VP, VP], I),

@@ -720,6 +720,30 @@ def make_activation_scene(n_active: int = 1500, n_immature: int = 3000, n_frames
         ef_nPoints=n_active, currentMinActDist=currentMinActDist)
 
 
+def make_window_activation_scene(n_active: int = 300, n_immature: int = 600, n_frames: int = 4, width: int = 320,
+                                 height: int = 240, seed: int = 7, kitti: bool = False,
+                                 currentMinActDist: float = 2.0):
+    """(BAScene, ActivationScene): make_activation_scene's scene together with the BA window it stands on -- the
+    BAScene make_activation_scene builds internally (same arguments, same seed), so the ActivationScene's MapPoints
+    are the window's points and its images the window's.  For the chain tracer -> activation -> window
+    (ImmatureTracer.activate_into): there the frames' KRKi / Kt and the pairs' precalcs are formed from the window's
+    own poses and affine states, which replace the ActivationScene's KRKi1 / Kt1 / RTll / tTll / aff.
+    The window's frames get brightness offsets b in [-2, 2] on the odd frames (aff_g2l a stays 0 and the exposures 1:
+    PRE_aff_mode = (1, b_target - b_host), free of exp()), and the ActivationScene's `aff` is set to match."""
+    bs = make_ba_scene(n_points=n_active, n_frames=n_frames, width=width, height=height, seed=seed, kitti=kitti,
+                       pose_noise=(0.001, 0.0005))
+    s = make_activation_scene(n_active=n_active, n_immature=n_immature, n_frames=n_frames, width=width, height=height,
+                              seed=seed, kitti=kitti, currentMinActDist=currentMinActDist)
+    assert np.array_equal(bs.pt_u, s.act_u) and np.array_equal(bs.pt_idepth, s.act_idepth)
+    rng = np.random.default_rng(seed + 41)
+    b = np.where(np.arange(n_frames) % 2 == 1, rng.uniform(-2.0, 2.0, n_frames), 0.0)
+    scale_b = 1000.0  # SCALE_B: state_scaled[7] = SCALE_B * state[7] is aff_g2l().b
+    bs.frames_state[:, 7] = b / scale_b
+    bs.frames_state_zero[:, 7] = b / scale_b
+    s.aff = np.array([[1.0, b[t] - b[h]] for h in range(n_frames) for t in range(n_frames)], np.float32)
+    return bs, s
+
+
 def make_select_frames(n_frames: int = 3, width: int = 640, height: int = 480, seed: int = SEED,
                        quantize: bool = False, flat_frac: float = 0.0, contrast_ramp: bool = False):
     """Raw level-0 frames for PixelSelector::makeMaps (Src/PixelSelector.cpp:118-262): the textured planes seen from

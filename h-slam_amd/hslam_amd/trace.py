@@ -180,6 +180,69 @@ class ImmatureTracer:
         check(self.lib.hs_tracer_compact(self.h, ptr(k)))
         self.n = int(k.astype(bool).sum())
 
+    # the same activation with a BAWindow as its window, device to device (hs_tracer_activate_ba)
+    def activate_into(self, ba, slots, flagged, currentMinActDist, order=None, compact=True, drop_slot=None):
+        """activatePointsMT over the stored points into ``ba`` (hslam_amd.ba.BAWindow, incremental, single-rank):
+        K, the active points and the frames' / pairs' precalcs come from the window on the device, every activated
+        point enters the window (committed by the next makeIDX) with its IN residuals, and with ``compact`` the
+        tracer drops the points that are not kept and those on the slots marked in ``drop_slot`` ([64] flags).
+        slots / flagged: per window frame, the tracer image slot and FlaggedForMarginalization.
+        Returns dict(action [n before the compaction], handles (toOptimize order), n_activated, n_deleted,
+        currentMinActDist)."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        fl = np.ascontiguousarray(flagged, np.int32)
+        assert len(sl) == len(fl)
+        od = None if order is None else np.ascontiguousarray(order, np.int32)
+        ds = None if drop_slot is None else np.ascontiguousarray(drop_slot, np.uint8)
+        assert ds is None or len(ds) == 64
+        n = self.n
+        action, handles = np.zeros(n, np.uint8), np.zeros(max(n, 1), np.int32)
+        cmad = C.c_float(currentMinActDist)
+        na, nd = C.c_int(), C.c_int()
+        check(self.lib.hs_tracer_activate_ba(self.h, ba.h, len(sl), ptr(sl), ptr(fl), C.byref(cmad),
+                                             0 if od is None else len(od), ptr(od), int(bool(compact)), ptr(ds),
+                                             ptr(action), ptr(handles), C.byref(na), C.byref(nd)))
+        if compact:
+            self.n = self._count()
+        return dict(action=action, handles=handles[: na.value].copy(), n_activated=na.value, n_deleted=nd.value,
+                    currentMinActDist=cmad.value)
+
+    def _count(self):
+        m = C.c_int()
+        check(self.lib.hs_tracer_get_points(self.h, C.byref(m), *([None] * 10)))
+        return m.value
+
+    def compact_device(self, keep=None, drop_slot=None):
+        """hs_tracer_compact on the device: keep (flags per point; None: the points the last activate_into left
+        KEEP) and not on a slot marked in drop_slot ([64] flags).  Returns the number of points left."""
+        k = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+        assert k is None or len(k) == self.n
+        ds = None if drop_slot is None else np.ascontiguousarray(drop_slot, np.uint8)
+        assert ds is None or len(ds) == 64
+        left = C.c_int()
+        check(self.lib.hs_tracer_compact_device(self.h, ptr(k), ptr(ds), C.byref(left)))
+        self.n = left.value
+        return self.n
+
+    def act_inputs(self, ba, points=True):
+        """What the last activate_into(ba, ...) formed and read: dict(K4, frames, pairs[, act_frame, act_u, act_v,
+        act_idepth]).  The point arrays only until ``ba`` is committed again (ask before makeIDX)."""
+        k4 = np.zeros(4, np.float32)
+        nF, na = C.c_int(), C.c_int()
+        check(self.lib.hs_tracer_get_act_inputs(self.h, ba.h, ptr(k4), C.byref(nF), None, None, C.byref(na),
+                                                None, None, None, None))
+        fr = np.zeros(nF.value, ACT_FRAME_DT)
+        pr = np.zeros(nF.value * nF.value, ACT_PAIR_DT)
+        n = na.value if points else 0
+        af = np.zeros(n, np.int32)
+        au, av, ai = (np.zeros(n, np.float32) for _ in range(3))
+        pp = [ptr(a) if points else None for a in (af, au, av, ai)]
+        check(self.lib.hs_tracer_get_act_inputs(self.h, ba.h, None, None, ptr(fr), ptr(pr), None, *pp))
+        o = dict(K4=k4, frames=fr, pairs=pr)
+        if points:
+            o.update(act_frame=af, act_u=au, act_v=av, act_idepth=ai)
+        return o
+
     def reinit(self):
         """ImmaturePoint ctor again on every stored point (a fresh first-trace state), on the device."""
         check(self.lib.hs_tracer_reinit(self.h))

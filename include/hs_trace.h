@@ -20,6 +20,10 @@
  *                          point.  The MapPoint / PointFrameResidual objects themselves are built by the caller
  *                          from the outputs (activated flag, idepth, IN-residual mask).
  *
+ *   hs_tracer_activate_ba  the same call with a BA context (include/hs_ba.h) as its window, device to device: the
+ *                          inputs from the window, the new MapPoints with their residuals (Src/Mapping.cpp:440-455,
+ *                          Src/FullSystemOptPoint.cpp:142-169) into it, the immature points' removal on the device.
+ *
  * Conventions as include/hs_ba.h: status codes (hs_types.h), caller-owned host buffers copied in/out,
  * the context owns device memory and its own HIP stream, single caller.  Images are Frame::DirPyr[0]:
  * W*H (I, dI/dx, dI/dy) float triplets.  Points are held in the order they are added.
@@ -27,6 +31,7 @@
 #ifndef HS_TRACE_H
 #define HS_TRACE_H
 
+#include "hs_ba.h" /* hs_ctx (the BA context of hs_tracer_activate_ba) */
 #include "hs_types.h"
 
 #ifdef __cplusplus
@@ -124,6 +129,44 @@ int hs_tracer_activate(hs_tracer* t, const float K4[4], int nF, const hs_act_fra
 int hs_tracer_get_distance_map(hs_tracer* t, float* dist);
 /* drop the points with keep[i] == 0; the survivors keep their relative order */
 int hs_tracer_compact(hs_tracer* t, const uint8_t* keep);
+
+/* ---- point activation into a BA window -------------------------------------------------------------------- */
+
+/* One activatePointsMT call whose window is the BA context's (single-rank, same device, same image size): the
+   device-to-device form of hs_tracer_activate + hs_tracer_get_points + hs_ba_insert_points + hs_ba_insert_residuals
+   (+ hs_tracer_compact).  Legal with structural edits pending (AddKeyframe: after insertFrame and
+   hs_ba_add_residuals_to_newest, before makeIDX): the call commits them first, so the newest frame is on the device;
+   the points it activates are committed by the caller's next makeIDX.
+     read from the BA on the device: K4 (its calibration), ef_nPoints (its point count), the active points (its point
+       set's host frame / u / v / idepth, read where they lie), hs_act_frame.KRKi / Kt and the hs_act_pair records
+       (formed by a kernel from the frames' PRE_worldToCam / PRE_camToWorld and affine states)
+     slots[nF], flagged_for_marg[nF]: per window frame, the tracer image slot and Frame::FlaggedForMarginalization
+     order[n_order], *currentMinActDist: as hs_tracer_activate
+   Every activated point is staged on the device (u, v, idepth = idepth_zero = the optimised idepth, no depth prior,
+   maxRelBaseline 0, numGoodResiduals 0, the immature point's colour and weights) and entered into the BA's window:
+   a new handle, hosted on the point's window frame, an IN residual into every frame of its IN mask in ascending frame
+   order, lastResiduals as hs_ba_insert_residuals sets them.  Read back: action and IN mask per tracer point, the
+   toOptimize list.
+     compact != 0: the tracer then drops, on the device, every point whose action is not HS_ACT_KEEP and every point
+       on a slot with drop_slot[slot] != 0 (drop_slot: NULL or 64 bytes); the survivors keep their order
+   Outputs (nullable): action_out[n points before the compaction], handles_out[*n_activated] the new handles in
+   toOptimize order, *n_activated, *n_deleted.
+   Errors leave the window and the tracer's points as they were: a multi-rank context HS_ERR_STATE; another device,
+   nF != the window's frames, a slot without an image HS_ERR_INVALID; window points + activated > the reserved
+   capacity HS_ERR_NOMEM (nothing staged, nothing compacted, *currentMinActDist unchanged). */
+int hs_tracer_activate_ba(hs_tracer* t, hs_ctx* ba, int nF, const int* slots, const int* flagged_for_marg,
+                          float* currentMinActDist, int n_order, const int* order, int compact,
+                          const uint8_t* drop_slot, uint8_t* action_out, int* handles_out, int* n_activated,
+                          int* n_deleted);
+/* the compaction alone: keep[i] != 0 (keep == NULL: the points the last hs_tracer_activate_ba left HS_ACT_KEEP;
+   HS_ERR_STATE when there is none for these points) and not drop_slot[slot] (nullable).  Stable: a two-level
+   exclusive scan of the keep flags, then a scatter of every per-point array into a second buffer set. */
+int hs_tracer_compact_device(hs_tracer* t, const uint8_t* keep, const uint8_t* drop_slot, int* n_left);
+/* what the last hs_tracer_activate_ba on `ba` formed and read, all nullable: K4, nF, frames[nF], pairs[nF*nF],
+   n_active and the active points' window frame / u / v / idepth.  The point arrays are read from the BA's point
+   set: HS_ERR_STATE once the window was committed again (ask before makeIDX). */
+int hs_tracer_get_act_inputs(hs_tracer* t, hs_ctx* ba, float K4[4], int* nF, hs_act_frame* frames, hs_act_pair* pairs,
+                             int* n_active, int* act_frame, float* act_u, float* act_v, float* act_idepth);
 
 /* re-run the ImmaturePoint ctor on every point already added (same host / u / v, no upload): a fresh
    first-trace state (idepth_min 0, idepth_max NaN, quality 10000, IPS_UNINITIALIZED) */
