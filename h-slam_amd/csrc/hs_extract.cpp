@@ -11,7 +11,9 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_extract.h"
 #include "hs_extract_kernels.h"
+#include "../../include/hs_image.h"
 #include "hs_host.h"
+#include "hs_image_kernels.h"
 #include "hs_sel_kernels.h"
 #include "hs_undist_kernels.h"
 
@@ -270,6 +272,22 @@ int hs_extractor_extract_u8(hs_extractor* e, hs_selector* s, hs_undistorter* u, 
   HS_TRY(begin_extract(e));
   HS_HIP(hipStreamWaitEvent(e->stream, ready, 0));
   return run_extract(e, d_map, u, raw, n_keys);
+}
+
+// The same, with cvImgL copied device to device from a device image (include/hs_image.h) behind its last set.
+int hs_extractor_extract_image(hs_extractor* e, hs_selector* s, hs_image* im, int* n_keys) {
+  if (!e || !s || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, e->device, e->W, e->H, 1, true, &v));
+  const float* d_map = nullptr;
+  hipEvent_t ready = nullptr;
+  HS_TRY(hs_select_device_map(s, e->device, e->W, e->H, &d_map, &ready));
+  HS_TRY(begin_extract(e));
+  HS_HIP(hipStreamWaitEvent(e->stream, ready, 0));
+  HS_HIP(hipStreamWaitEvent(e->stream, v.ready, 0));
+  HS_HIP(hipMemcpyAsync(e->d_img, v.img8, (size_t)e->W * e->H, hipMemcpyDeviceToDevice, e->stream));
+  HS_HIP(hs_image_consumed(im, e->stream));
+  return run_extract(e, d_map, nullptr, nullptr, n_keys);
 }
 
 int hs_extractor_get(hs_extractor* e, int* n, float* xy, float* angle, uint8_t* desc, uint8_t* blurred) {

@@ -8,9 +8,11 @@
 
 #include "../../include/hs_ba.h"
 #include "../../include/hs_flow.h"
+#include "../../include/hs_image.h"
 #include "hs_extract_kernels.h"
 #include "hs_flow_kernels.h"
 #include "hs_host.h"
+#include "hs_image_kernels.h"
 #include "hs_undist_kernels.h"
 
 // one frame: every level's image with its reflected border, and its derivative with a zero border
@@ -330,6 +332,20 @@ int hs_flow_track_u8(hs_flow* f, hs_undistorter* u, const uint8_t* raw, float ma
   HS_HIP(hipSetDevice(f->device));
   HS_HIP(hipEventRecord(f->e0, f->stream));
   HS_HIP(hs_undist_enqueue(u, f->stream, raw, nullptr, f->d_raw));
+  return run_track(f, f->d_raw, max_l1_error, n_good);
+}
+
+// The same, with cvImgL copied device to device from a device image (include/hs_image.h) behind its last set.
+int hs_flow_track_image(hs_flow* f, hs_image* im, float max_l1_error, int* n_good) {
+  if (!f || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, f->device, f->W, f->H, 1, true, &v));
+  HS_TRY(need_first(f));
+  HS_HIP(hipSetDevice(f->device));
+  HS_HIP(hipStreamWaitEvent(f->stream, v.ready, 0));
+  HS_HIP(hipEventRecord(f->e0, f->stream));
+  HS_HIP(hipMemcpyAsync(f->d_raw, v.img8, (size_t)f->W * f->H, hipMemcpyDeviceToDevice, f->stream));
+  HS_HIP(hs_image_consumed(im, f->stream));
   return run_track(f, f->d_raw, max_l1_error, n_good);
 }
 

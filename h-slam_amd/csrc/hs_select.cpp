@@ -14,6 +14,8 @@
 #include "hs_host.h"
 #include "hs_pyr_kernels.h"
 #include "hs_sel_kernels.h"
+#include "../../include/hs_image.h"
+#include "hs_image_kernels.h"
 
 struct hs_selector : hs::Device {
   hs_params P;
@@ -281,6 +283,31 @@ extern "C" int hs_selector_make_maps_raw(hs_selector* s, int frame_id, const flo
   HS_HIP(hipMemcpyAsync(s->d_raw, img, area * sizeof(float), hipMemcpyHostToDevice, s->stream));
   HS_HIP(hipEventRecord(s->e0, s->stream));
   HS_HIP(hs_build_dir_pyramid(s->stream, s->d_raw, s->W, s->H, 3, s->d_lvl, s->d_g));
+  s->last_passes = 0;
+  s->have_map = false;
+  int n = 0;
+  HS_TRY(make_maps(s, reinterpret_cast<const float*>(s->d_lvl[0]), 4, frame_id, density, recursions_left, th_factor,
+                   &n));
+  return finish(s, map_out, n_selected, n);
+}
+
+// The same from a device image (include/hs_image.h): level 0's texels and absSquaredGrad[0..2] copied device to
+// device behind the image's last set, in place of the upload and the pyramid; makeMaps and its waits are shared.
+extern "C" int hs_selector_make_maps_image(hs_selector* s, int frame_id, hs_image* im, float density,
+                                           int recursions_left, float th_factor, float* map_out, int* n_selected) {
+  HS_TRY(check_args(s, density, th_factor));
+  if (!im) return hs::fail(HS_ERR_INVALID, "null image");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, s->device, s->W, s->H, 3, false, &v));
+  HS_HIP(hipSetDevice(s->device));
+  HS_HIP(hipStreamWaitEvent(s->stream, v.ready, 0));
+  HS_HIP(hipEventRecord(s->e0, s->stream));
+  HS_HIP(hipMemcpyAsync(s->d_lvl[0], v.lvl[0], sizeof(float4) * (size_t)s->W * s->H, hipMemcpyDeviceToDevice,
+                        s->stream));
+  for (int l = 0; l < 3; l++)
+    HS_HIP(hipMemcpyAsync(s->d_g[l], v.absg[l], sizeof(float) * (size_t)(s->W >> l) * (s->H >> l),
+                          hipMemcpyDeviceToDevice, s->stream));
+  HS_HIP(hs_image_consumed(im, s->stream));
   s->last_passes = 0;
   s->have_map = false;
   int n = 0;

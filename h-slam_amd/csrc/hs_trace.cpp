@@ -20,6 +20,8 @@
 #include "hs_undist_kernels.h"
 #include "../../include/hs_extract.h"
 #include "hs_extract_kernels.h"
+#include "../../include/hs_image.h"
+#include "hs_image_kernels.h"
 
 #define HS_MAXF_ACT 8                        // activation window (nF <= 8 keyframes)
 #define HS_ACT_LDS_MAP_MAX (156 * 1024)     // level-1 distance map in LDS up to this size
@@ -186,15 +188,20 @@ void hs_tracer_destroy(hs_tracer* t) {
   delete t;
 }
 
+// host slot `slot`'s image buffer, allocated and entered in the device table on first use
+static int host_slot(hs_tracer* t, int slot) {
+  if (t->d_host_img[slot]) return HS_OK;
+  HS_TRY(t->pool.alloc(&t->d_host_img[slot], (size_t)t->W * t->H));
+  // (the source is a member: it keeps its value and outlives the copy, whenever the stream gets to it)
+  HS_HIP(hipMemcpyAsync(t->d_host_tab + slot, &t->d_host_img[slot], sizeof(float4*), hipMemcpyHostToDevice, t->stream));
+  return HS_OK;
+}
+
 int hs_tracer_set_host_image(hs_tracer* t, int slot, const float* img) {
   if (!t || !img) return hs::fail(HS_ERR_INVALID, "null argument");
   if (slot < 0 || slot >= HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "host slot out of range");
   HS_HIP(hipSetDevice(t->device));
-  if (!t->d_host_img[slot]) {
-    HS_TRY(t->pool.alloc(&t->d_host_img[slot], (size_t)t->W * t->H));
-    HS_HIP(hipMemcpyAsync(t->d_host_tab + slot, &t->d_host_img[slot], sizeof(float4*), hipMemcpyHostToDevice,
-                          t->stream));
-  }
+  HS_TRY(host_slot(t, slot));
   return upload_img(t, t->d_host_img[slot], img);
 }
 
@@ -313,6 +320,35 @@ int hs_tracer_set_frame_u8(hs_tracer* t, hs_undistorter* u, const uint8_t* raw) 
   HS_HIP(hipStreamSynchronize(t->stream));
   t->have_frame = true;
   return HS_OK;
+}
+
+// level 0 of a device image (include/hs_image.h) into one of the tracer's own level-0 buffers, device to device
+// behind the image's last set; no host wait (every reader of dst runs on the tracer's stream)
+static int copy_image_level0(hs_tracer* t, float4* dst, hs_image* im, const HsImageView& v) {
+  HS_HIP(hipStreamWaitEvent(t->stream, v.ready, 0));
+  HS_HIP(hipMemcpyAsync(dst, v.lvl[0], sizeof(float4) * (size_t)t->W * t->H, hipMemcpyDeviceToDevice, t->stream));
+  HS_HIP(hs_image_consumed(im, t->stream));
+  return HS_OK;
+}
+
+int hs_tracer_set_frame_image(hs_tracer* t, hs_image* im) {
+  if (!t || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, t->device, t->W, t->H, 1, false, &v));
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(copy_image_level0(t, t->d_new, im, v));
+  t->have_frame = true;
+  return HS_OK;
+}
+
+int hs_tracer_set_host_image_from(hs_tracer* t, int slot, hs_image* im) {
+  if (!t || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (slot < 0 || slot >= HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "host slot out of range");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, t->device, t->W, t->H, 1, false, &v));
+  HS_HIP(hipSetDevice(t->device));
+  HS_TRY(host_slot(t, slot));
+  return copy_image_level0(t, t->d_host_img[slot], im, v);
 }
 
 int hs_tracer_trace(hs_tracer* t, int n_hosts, const hs_trace_host* hosts, int counts6[6]) {

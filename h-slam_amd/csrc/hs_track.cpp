@@ -17,6 +17,8 @@
 #include "hs_pyr_kernels.h"
 #include "../../include/hs_undist.h"
 #include "hs_undist_kernels.h"
+#include "../../include/hs_image.h"
+#include "hs_image_kernels.h"
 
 // a captured makeCoarseDepthL0 (make_depth_l0 from a device count): ~32 launches and copies, replayed as one graph;
 // keyed by everything its launches bake in (the reference pyramid's level pointers swap on a promoted frame)
@@ -544,6 +546,21 @@ int hs_tracker_frame_to_ba(hs_tracker* t, hs_ctx* ba, int frame) {
   return HS_OK;
 }
 
+// The same hand-off from a device image (include/hs_image.h), for a keyframe whose frame no tracker holds: the BA
+// stream waits for the image's last set, the copy and the packed slot run on the BA stream, and the image's next set
+// waits for the copy.
+int hs_image_to_ba(hs_image* im, hs_ctx* ba, int frame) {
+  if (!im || !ba) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, ba->device, ba->cam.width, ba->cam.height, 1, false, &v));
+  HS_HIP(hipSetDevice(ba->device));
+  HS_HIP(hipStreamWaitEvent(ba->stream, v.ready, 0));
+  if (const int rc = hs::copy_frame_image_device(ba, frame, v.lvl[0]))
+    return hs::fail(rc, std::string("hs_image_to_ba: ") + hs::g_err);
+  HS_HIP(hs_image_consumed(im, ba->stream));
+  return HS_OK;
+}
+
 int hs_tracker_set_event_timing(hs_tracker* t, int on) {
   if (!t) return hs::fail(HS_ERR_INVALID, "null tracker");
   t->evt = on ? 1 : 0;
@@ -596,6 +613,23 @@ int hs_tracker_set_frame_u8(hs_tracker* t, hs_undistorter* u, const uint8_t* raw
   HS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
   HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
   HS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
+  t->newExposure = ab_exposure;
+  t->haveFrame = true;
+  return HS_OK;
+}
+
+// The same frame from a device image (include/hs_image.h): every level copied device to device behind the image's
+// last set, nothing built here and no host wait -- whatever reads d_new next runs on this stream.
+int hs_tracker_set_frame_image(hs_tracker* t, hs_image* im, float ab_exposure) {
+  if (!t || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, t->device, t->W, t->H, t->nlev, false, &v));
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipStreamWaitEvent(t->stream, v.ready, 0));
+  for (int l = 0; l < t->nlev; l++)
+    HS_HIP(hipMemcpyAsync(t->d_new[l], v.lvl[l], sizeof(float4) * (size_t)t->w[l] * t->h[l], hipMemcpyDeviceToDevice,
+                          t->stream));
+  HS_HIP(hs_image_consumed(im, t->stream));
   t->newExposure = ab_exposure;
   t->haveFrame = true;
   return HS_OK;

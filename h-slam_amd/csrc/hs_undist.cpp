@@ -44,6 +44,20 @@ int hs_undist_match(const hs_undistorter* u, int device, int w, int h) {
   return HS_OK;
 }
 
+void hs_undist_tables(const hs_undistorter* u, HsUndistArgs* a) {
+  a->w_in = u->w_in;
+  a->h_in = u->h_in;
+  a->n_out = u->w_out * u->h_out;
+  a->passthrough = u->passthrough ? 1 : 0;
+  a->raw = nullptr;
+  a->map = u->d_map;
+  a->Binv = u->have_gamma ? u->d_Binv : nullptr;
+  a->B = (u->have_gamma || u->have_vig) ? u->d_B : nullptr;
+  a->vinv = u->have_vig ? u->d_vinv : nullptr;
+  a->fimg = nullptr;
+  a->img8 = nullptr;
+}
+
 hipError_t hs_undist_enqueue(hs_undistorter* u, hipStream_t stream, const uint8_t* raw, float* d_fimg,
                              uint8_t* d_img8) {
   const size_t n_in = (size_t)u->w_in * u->h_in;
@@ -52,15 +66,8 @@ hipError_t hs_undist_enqueue(hs_undistorter* u, hipStream_t stream, const uint8_
     if (e != hipSuccess) return e;
   }
   HsUndistArgs a;
-  a.w_in = u->w_in;
-  a.h_in = u->h_in;
-  a.n_out = u->w_out * u->h_out;
-  a.passthrough = u->passthrough ? 1 : 0;
+  hs_undist_tables(u, &a);
   a.raw = u->d_in;
-  a.map = u->d_map;
-  a.Binv = u->have_gamma ? u->d_Binv : nullptr;
-  a.B = (u->have_gamma || u->have_vig) ? u->d_B : nullptr;
-  a.vinv = u->have_vig ? u->d_vinv : nullptr;
   a.fimg = d_fimg;
   a.img8 = d_img8;
   hipLaunchKernelGGL(hs_k_undistort, dim3((a.n_out + 255) / 256), dim3(256), 0, stream, a);

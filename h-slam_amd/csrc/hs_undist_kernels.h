@@ -23,6 +23,10 @@ __global__ void hs_k_undistort(HsUndistArgs a);
 
 // Checks that u is on `device` with a w x h output; HS_ERR_INVALID with hs_last_error set otherwise.
 int hs_undist_match(const hs_undistorter* u, int device, int w, int h);
+// The tables where they lie on the device, for a caller that brings its own staging of the raw frame and its own
+// stream (hs_image_set_u8): every field of HsUndistArgs but raw, fimg and img8, which are left null.  The tables are
+// read-only between hs_undistorter_set_photometric / _set_remap calls, so any number of streams may read them.
+void hs_undist_tables(const hs_undistorter* u, HsUndistArgs* a);
 // Enqueues on `stream`: upload of the raw u8 frame (null: keep the staged one) into u's input staging, then the kernel into d_fimg
 // (w_out*h_out floats, device) and d_img8 (nullable).  The caller synchronises `stream` before it returns to its
 // own caller (raw is the user's buffer, and the staging is reused by the next call).

@@ -224,6 +224,21 @@ SIGNATURES = {
     "hs_flow_calc": ([VP, VP, VP, I, VP, VP, VP, VP, VP], I),
     "hs_flow_get_pyramid": ([VP, I, I, VP, VP, VP, VP], I),
     "hs_flow_last_stats": ([VP, VP, VP, VP], I),
+    # include/hs_image.h
+    "hs_image_create": ([VP, I, I, I, I], I),
+    "hs_image_destroy": ([VP], None),
+    "hs_image_set_u8": ([VP, VP, VP], I),
+    "hs_image_set_raw": ([VP, VP], I),
+    "hs_image_get": ([VP, I, VP, VP, VP], I),
+    "hs_image_last_stats": ([VP, VP], I),
+    "hs_image_time_chain": ([VP, VP, VP, VP], I),
+    "hs_tracker_set_frame_image": ([VP, VP, C.c_float], I),
+    "hs_tracer_set_frame_image": ([VP, VP], I),
+    "hs_tracer_set_host_image_from": ([VP, I, VP], I),
+    "hs_selector_make_maps_image": ([VP, I, VP, C.c_float, I, C.c_float, VP, VP], I),
+    "hs_extractor_extract_image": ([VP, VP, VP, VP], I),
+    "hs_flow_track_image": ([VP, VP, C.c_float, VP], I),
+    "hs_image_to_ba": ([VP, VP, I], I),
 }
 
 _lib = None

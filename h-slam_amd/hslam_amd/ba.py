@@ -145,6 +145,15 @@ class BAWindow:
             tracker.frame_to_ba(self, idx - 1)
         return idx - 1
 
+    def set_frame_image_raw(self, frame: int, raw):
+        """Window frame `frame`'s image from a raw (h, w) float32 image, its level 0 built on the device."""
+        check(self.lib.hs_ba_set_frame_image_raw(self.h, int(frame), ptr(np.ascontiguousarray(raw, np.float32))))
+
+    def set_frame_image_from(self, frame: int, image):
+        """Window frame `frame`'s image from level 0 of a hslam_amd.image.DeviceImage, device to device and ordered
+        on the device both ways (hs_image_to_ba)."""
+        check(self.lib.hs_image_to_ba(image.h, self.h, int(frame)))
+
     def insertPoints(self, host, u, v, idepth, idepth_zero=None, color=None, weights=None, has_prior=None,
                      max_rel_baseline=None, num_good=None):
         """EnergyFunctional::insertPoint for n points (host: window frame index).  Returns their handles."""

@@ -6,6 +6,7 @@ cvImgL, and each key's intensity-centroid angle and 256-bit rotated-BRIEF descri
     n = ex.extract(selectionMap, cvImgL)                   # host map and image
     n = ex.extract_selected(selector, cvImgL)              # the map of selector's last makeMaps, read on the device
     n = ex.extract_u8(selector, undistorter, raw)          # cvImgL made from the camera's raw frame on the device
+    n = ex.extract_image(selector, image)                  # cvImgL of a DeviceImage (hslam_amd.image), on the device
     r = ex.get()                                           # dict(xy, angle, desc[, blurred])
     tracer.add_keys(ex, slot)                              # makeNewTraces: one ImmaturePoint per key, device to device
 """
@@ -84,6 +85,11 @@ class FeatureExtractor:
         a = self._img(raw, (undistorter.h_in, undistorter.w_in))
         n = C.c_int()
         return self._done(self.lib.hs_extractor_extract_u8(self.h, selector.h, undistorter.h, ptr(a), C.byref(n)), n)
+
+    def extract_image(self, selector, image) -> int:
+        """The same, cvImgL being that of a hslam_amd.image.DeviceImage set from a raw u8 frame, read on the device."""
+        n = C.c_int()
+        return self._done(self.lib.hs_extractor_extract_image(self.h, selector.h, image.h, C.byref(n)), n)
 
     def get(self, blurred: bool = False):
         """The last successful extract: dict(xy (n, 2) float32 = mvKeys[i].pt, angle (n,) float32 degrees,

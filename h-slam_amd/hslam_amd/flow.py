@@ -8,6 +8,7 @@ later frame, with the reference's bookkeeping of previous points, outputs and go
     n_good = fl.track(cvImgL, 7)                 # one FindMatches; or
     n_good = fl.track_extracted(extractor, 7)    # the new frame's cvImgL where the extractor left it; or
     n_good = fl.track_u8(undistorter, raw, 7)    # cvImgL made from the camera's raw frame on the device
+    n_good = fl.track_image(image, 7)            # cvImgL of a DeviceImage (hslam_amd.image), on the device
     r = fl.get()                                 # dict(first_xy, prev_xy, xy, status, err, good)
     m = fl.mean_flow()                           # ComputeMeanOpticalFlow(MatchedPtsBkp, MatchedPts)
     r = fl.calc(prev8, next8, prev_xy[, init_xy])  # one stand-alone calcOpticalFlowPyrLK: dict(xy, status, err)
@@ -82,6 +83,12 @@ class KeypointFlow:
         a = self._img(raw, (undistorter.h_in, undistorter.w_in))
         n = C.c_int()
         check(self.lib.hs_flow_track_u8(self.h, undistorter.h, ptr(a), max_l1_error, C.byref(n)))
+        return n.value
+
+    def track_image(self, image, max_l1_error: float) -> int:
+        """One FindMatches against the cvImgL of a hslam_amd.image.DeviceImage set from a raw u8 frame."""
+        n = C.c_int()
+        check(self.lib.hs_flow_track_image(self.h, image.h, max_l1_error, C.byref(n)))
         return n.value
 
     def get(self):

@@ -4,7 +4,8 @@ The mirror keeps the reference's interface: ``PixelSelector(width, height)`` (th
 currentPotential = 3), ``makeMaps(DirPyr, id, GradPyr, density, recursionsLeft=1, thFactor=1)`` returning the
 selection map (0 / 1 / 2 / 4 per pixel, FeatureDetector's ``selectionMap``) and numHaveSub, and
 ``currentPotential`` as a read/write attribute.  ``makeMapsRaw`` takes the undistorted level-0 image instead and
-builds the pyramid on the device (Frame::CreateDirPyrs, include/hs_pyr.h).
+builds the pyramid on the device (Frame::CreateDirPyrs, include/hs_pyr.h); ``makeMapsImage`` reads the levels of a
+``hslam_amd.image.DeviceImage`` where they lie (include/hs_image.h).
 """
 from __future__ import annotations
 
@@ -54,6 +55,16 @@ class PixelSelector:
         n = C.c_int()
         check(self.lib.hs_selector_make_maps_raw(self.h, int(id), ptr(img), float(density), int(recursionsLeft),
                                                  float(thFactor), ptr(out) if want_map else None, C.byref(n)))
+        return out, n.value
+
+    def makeMapsImage(self, image, id: int, density: float, recursionsLeft: int = 1, thFactor: float = 1.0,
+                      want_map: bool = True):
+        """makeMaps on a hslam_amd.image.DeviceImage (>= 3 levels): its level 0 and absSquaredGrad[0..2] are read
+        on the device (hs_selector_make_maps_image)."""
+        out = np.empty((self.H, self.W), np.float32) if want_map else None
+        n = C.c_int()
+        check(self.lib.hs_selector_make_maps_image(self.h, int(id), image.h, float(density), int(recursionsLeft),
+                                                   float(thFactor), ptr(out) if want_map else None, C.byref(n)))
         return out, n.value
 
     @property

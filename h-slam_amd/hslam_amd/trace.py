@@ -77,6 +77,15 @@ class ImmatureTracer:
         assert a.shape == (self.H, self.W, 3)
         check(self.lib.hs_tracer_set_host_image(self.h, slot, ptr(a)))
 
+    def set_host_image_from(self, slot: int, image):
+        """Host slot `slot`'s DirPyr[0] from a hslam_amd.image.DeviceImage, device to device
+        (hs_tracer_set_host_image_from)."""
+        check(self.lib.hs_tracer_set_host_image_from(self.h, int(slot), image.h))
+
+    def set_frame_image(self, image):
+        """The frame to trace on from a hslam_amd.image.DeviceImage, device to device (hs_tracer_set_frame_image)."""
+        check(self.lib.hs_tracer_set_frame_image(self.h, image.h))
+
     def add_points(self, host, u, v):
         h = np.ascontiguousarray(host, np.int32)
         uu = np.ascontiguousarray(u, np.float32)

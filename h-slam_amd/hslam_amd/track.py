@@ -73,6 +73,13 @@ class CoarseTracker:
         assert a.shape == (undistorter.h_in, undistorter.w_in)
         check(self.lib.hs_tracker_set_frame_u8(self.h, undistorter.h, ptr(a), float(ab_exposure)))
 
+    def setNewFrameImage(self, image, ab_exposure):
+        """The frame to track as a hslam_amd.image.DeviceImage: every level copied device to device, no host wait
+        (hs_tracker_set_frame_image)."""
+        check(self.lib.hs_tracker_set_frame_image(self.h, image.h, float(ab_exposure)))
+
+    set_frame_image = setNewFrameImage
+
     def setCoarseTrackingRefBA(self, ba, promote: bool, ab_exposure=1.0, aff_g2l=(0.0, 0.0)):
         """setCoarseTrackingRef from a BA context (hslam_amd.ba.BAWindow) on the device: the points with an IN
         residual into its newest frame, no host round trip.  promote: the frame last set here becomes the reference
