@@ -14,6 +14,7 @@
 //                     scatter of every array into the second buffer set (one lane per (point, component)).
 #include <hip/hip_runtime.h>
 
+#include "hs_imm_ctor.h"
 #include "hs_kernels.h"
 #include "hs_trace_kernels.h"
 #include "hs_win_kernels.h"
@@ -35,23 +36,7 @@ __global__ __launch_bounds__(64) void hs_k_act_form(HsActFormArgs a) {
   }
 }
 
-// exclusive prefix of `take` over the workgroup's threads in thread order; *total = the workgroup's count.
-// wsum: one int per wave (shared).  Ends with a barrier, so wsum may be reused at once.
-__device__ __forceinline__ int block_rank(bool take, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  const unsigned long long m = __ballot(take);
-  if (lane == 0) wsum[wv] = __popcll(m);
-  __syncthreads();
-  int off = 0, all = 0;
-  for (int w = 0; w < nw; w++) {
-    const int s = wsum[w];
-    off += w < wv ? s : 0;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return off + __popcll(m & ((1ull << lane) - 1ull));
-}
+using hs_imm::block_rank;
 
 __global__ __launch_bounds__(1024) void hs_k_act_stage(HsActStageArgs a) {
   __shared__ int wsum[16];

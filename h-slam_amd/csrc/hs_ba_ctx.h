@@ -304,6 +304,11 @@ int commit(hs_ctx* c);            // hs_ba_window.cpp: apply pending structural 
 // before it changes anything; handles_out (nullable) receives the new handles.
 int stage_activated(hs_ctx* c, int n, const int* host, const uint8_t* res_in, int* handles_out);
 int mirror_points(hs_ctx* c);     // points the mirror holds (committed and staged)
+// hs_ba_window.cpp: the mirror's part of hs_refiner_seed_ba.  seed_frame_check: the context has a window and `frame`
+// is one of its frames (HS_ERR_STATE / HS_ERR_INVALID; no device work).  stage_seeded: n points staged on the device at
+// d_act_stage[n_dev_staged ...], hosted on `frame`, no residuals, lastResiduals (none, IN) twice.
+int seed_frame_check(hs_ctx* c, int frame);
+int stage_seeded(hs_ctx* c, int n, int frame, int* handles_out);
 inline int commit_if_dirty(hs_ctx* c) { return c->dirty ? commit(c) : HS_OK; }
 int max_blocks_for(int capP);
 // everything enqueued on the context's stream has finished: hipStreamSynchronize on a single-rank context; on a

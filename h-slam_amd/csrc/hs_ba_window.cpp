@@ -938,6 +938,25 @@ int stage_activated(hs_ctx* c, int n, const int* host, const uint8_t* res_in, in
   return HS_OK;
 }
 
+// System::InitFromInitializer's new MapPoints (Src/System.cpp:277-289) in the mirror: hs::stage_activated's points on
+// window frame `frame` without a residual.  The one difference is lastResiduals: the reference's pairs are
+// value-initialised here, (none, ResState::IN), where activation writes (none, OOB).
+int seed_frame_check(hs_ctx* c, int frame) {
+  HS_TRY(ensure_incremental(c));
+  if (frame < 0 || frame >= (int)c->wframes.size()) return fail(HS_ERR_INVALID, "seeded points on no window frame");
+  return HS_OK;
+}
+
+int stage_seeded(hs_ctx* c, int n, int frame, int* handles_out) {
+  HS_TRY(seed_frame_check(c, frame));
+  const std::vector<int> host((size_t)std::max(n, 1), frame);
+  const std::vector<uint8_t> none((size_t)std::max(n, 1), 0);
+  HS_TRY(stage_activated(c, n, host.data(), none.data(), handles_out));
+  auto& v = c->wpts[frame];  // the new points are the list's last n
+  for (size_t k = v.size() - (size_t)n; k < v.size(); k++) v[k].last_code[0] = v[k].last_code[1] = (uint8_t)HS_RES_IN;
+  return HS_OK;
+}
+
 }  // namespace hs
 
 // test hook (not in the header, no device work): the mirror rule of hs::stage_activated (out_a) beside

@@ -213,6 +213,15 @@ int need_first(const hs_flow* f) {
 
 }  // namespace
 
+bool hs_flow_first_points(hs_flow* f, int* device, int* W, int* H, int* n, const float2** d_first) {
+  *device = f->device;
+  *W = f->W;
+  *H = f->H;
+  *n = f->n;
+  *d_first = f->d_first;
+  return f->have_first;
+}
+
 extern "C" {
 
 int hs_flow_create(hs_flow** out, int device_id, int width, int height, int capacity) {

@@ -61,3 +61,10 @@ __global__ void hs_k_flow_pad(HsFlowPadArgs a);
 __global__ void hs_k_flow_pyrdown(HsFlowDownArgs a);
 __global__ void hs_k_flow_scharr(HsFlowScharrArgs a);
 __global__ void hs_k_flow_lk(HsFlowLkArgs a);
+
+// FirstFramePts (= mvKeys[i].pt, n pairs) where the last hs_flow_set_first* left them on the device; false before
+// the first one.  Every hs_flow entry waits for its own work before it returns, so the pairs are complete; only the
+// next hs_flow_set_first* rewrites them, so a consumer waits for its own reads before it returns
+// (hs_refiner_set_points_flow does, for its violation count).
+struct hs_flow;
+bool hs_flow_first_points(hs_flow* f, int* device, int* W, int* H, int* n, const float2** d_first);

@@ -1,6 +1,8 @@
 // hs_refine.cpp — C-ABI implementation of the DirectRefinement boundary (include/hs_refine.h): refiner
 // context, device frames and point state (structure of arrays), and the LM step launches (one kernel per
-// iteration, enqueued in batches; the device-side control block decides and stops).
+// iteration, enqueued in batches; the device-side control block decides and stops).  Also the initializer hand-off of
+// include/hs_init.h: the frames from a device image, the points from the flow context's first-frame keys, and
+// System::InitFromInitializer's point loop into a BA window.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,8 +13,14 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hs_init.h"
 #include "../../include/hs_refine.h"
+#include "hs_ba_ctx.h"
+#include "hs_flow_kernels.h"
 #include "hs_host.h"
+#include "hs_image_kernels.h"
+#include "hs_init_kernels.h"
+#include "hs_init_rule.h"
 #include "hs_refine_kernels.h"
 
 namespace {
@@ -43,7 +51,7 @@ struct hs_refiner : hs::Device {
   float4* d_img1 = nullptr;
   float4* d_img2 = nullptr;
   float expo1 = 0, expo2 = 0;
-  bool haveFrames = false;
+  bool have1 = false, have2 = false;  // FirstFrame / SecondFrame set (independently: hs_init.h)
   int n = 0, cap = 0;
   float* d_pf = nullptr;     // PF_COUNT planes of cap floats
   uint8_t* d_pb = nullptr;   // tri | good | good_new, cap bytes each
@@ -57,6 +65,12 @@ struct hs_refiner : hs::Device {
   int last_iters = 0;
   long long* d_trace = nullptr;  // HS_REF_TRACE=1: per-block stamps of each step launch, dumped to stderr
   double last_ms = 0;
+  // hs_refiner_seed_ba (allocated by its first call, regrown with the point count)
+  int seed_cap = 0;
+  uint8_t* d_why = nullptr;
+  uint8_t* h_why = nullptr;  // pinned
+  int* d_nseed = nullptr;
+  hipEvent_t ev_handoff = nullptr;  // refiner -> BA stream order (the staged points)
 };
 
 static HsRefPoints points_of(hs_refiner* r) {
@@ -133,8 +147,8 @@ static int read_ctl(hs_refiner* r) {
 }
 
 static int check_ready(hs_refiner* r) {
-  if (!r->haveFrames) return hs::fail(HS_ERR_STATE, "hs_refiner_set_frames first");
-  if (r->n <= 0) return hs::fail(HS_ERR_STATE, "hs_refiner_set_points first");
+  if (!r->have1 || !r->have2) return hs::fail(HS_ERR_STATE, "both frames first (hs_refiner_set_frames, or hs_refiner_set_first_image and _set_second_image)");
+  if (r->n <= 0) return hs::fail(HS_ERR_STATE, "hs_refiner_set_points / hs_refiner_set_points_flow first");
   HS_HIP(hipSetDevice(r->device));
   return HS_OK;
 }
@@ -188,6 +202,39 @@ static int run_refine(hs_refiner* r, const double T7[7], const double aff[2]) {
   return HS_OK;
 }
 
+// the state block of n points (the refiner then holds no points until the caller sets r->n)
+static int alloc_points(hs_refiner* r, int n) {
+  hs::Pool& m = r->pool;
+  m.release(&r->d_pf);
+  m.release(&r->d_pb);
+  m.release(&r->d_part);
+  m.release(&r->d_trace);
+  r->n = 0;
+  r->cap = n;  // planes of exactly n: the [2][n] energy blocks are two adjacent planes
+  const size_t nb = (size_t)((n + HS_REF_PPB - 1) / HS_REF_PPB);
+  HS_TRY(m.alloc(&r->d_pf, PF_COUNT * (size_t)n));
+  HS_TRY(m.alloc(&r->d_pb, 3 * (size_t)n));
+  HS_TRY(m.alloc(&r->d_part, HS_REF_NRED * nb));
+  if (const char* e = std::getenv("HS_REF_TRACE"); e && std::atoi(e) > 0) HS_TRY(m.alloc_zero(&r->d_trace, 16 * nb, r->stream));
+  return HS_OK;
+}
+
+// level 0 of a device image (include/hs_image.h) as FirstFrame / SecondFrame ->frame->DirPyr[0]: device to device behind
+// the image's last set, no host wait (every reader of dst runs on the refiner's stream)
+static int set_image(hs_refiner* r, hs_image* im, float4* hs_refiner::*dst, bool hs_refiner::*have,
+                     float hs_refiner::*expo, float ab_exposure) {
+  if (!r || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsImageView v;
+  HS_TRY(hs_image_view(im, r->device, r->W, r->H, 1, false, &v));
+  HS_HIP(hipSetDevice(r->device));
+  HS_HIP(hipStreamWaitEvent(r->stream, v.ready, 0));
+  HS_HIP(hipMemcpyAsync(r->*dst, v.lvl[0], sizeof(float4) * (size_t)r->W * r->H, hipMemcpyDeviceToDevice, r->stream));
+  HS_HIP(hs_image_consumed(im, r->stream));
+  r->*expo = ab_exposure;
+  r->*have = true;
+  return HS_OK;
+}
+
 extern "C" {
 
 int hs_refiner_create(hs_refiner** out, int device_id, int width, int height, const double K4[4]) {
@@ -217,6 +264,7 @@ void hs_refiner_destroy(hs_refiner* r) {
   (void)hipSetDevice(r->device);
   if (r->stream) (void)hipStreamSynchronize(r->stream);
   r->pool.release_all();
+  if (r->ev_handoff) (void)hipEventDestroy(r->ev_handoff);
   r->close();
   delete r;
 }
@@ -235,7 +283,7 @@ int hs_refiner_set_frames(hs_refiner* r, const float* first, const float* second
   }
   r->expo1 = e1;
   r->expo2 = e2;
-  r->haveFrames = true;
+  r->have1 = r->have2 = true;
   return HS_OK;
 }
 
@@ -245,18 +293,7 @@ int hs_refiner_set_points(hs_refiner* r, int n, const float* u, const float* v, 
     if (!std::isfinite(u[i]) || !std::isfinite(v[i]) || u[i] < 0 || v[i] < 0 || u[i] > r->W - 1 || v[i] > r->H - 1)
       return hs::fail(HS_ERR_INVALID, "keypoint outside the image");
   HS_HIP(hipSetDevice(r->device));
-  hs::Pool& m = r->pool;
-  m.release(&r->d_pf);
-  m.release(&r->d_pb);
-  m.release(&r->d_part);
-  m.release(&r->d_trace);
-  r->n = 0;
-  r->cap = n;  // planes of exactly n: the [2][n] energy blocks are two adjacent planes
-  const size_t nb = (size_t)((n + HS_REF_PPB - 1) / HS_REF_PPB);
-  HS_TRY(m.alloc(&r->d_pf, PF_COUNT * (size_t)n));
-  HS_TRY(m.alloc(&r->d_pb, 3 * (size_t)n));
-  HS_TRY(m.alloc(&r->d_part, HS_REF_NRED * nb));
-  if (const char* e = std::getenv("HS_REF_TRACE"); e && std::atoi(e) > 0) HS_TRY(m.alloc_zero(&r->d_trace, 16 * nb, r->stream));
+  HS_TRY(alloc_points(r, n));
   // the ctor's Pnt set-up (Src/Initializer.cpp:1362-1382)
   std::vector<float> pf((size_t)PF_COUNT * n, 0.f);
   std::vector<uint8_t> pb(3 * (size_t)n, 0);
@@ -277,6 +314,137 @@ int hs_refiner_set_points(hs_refiner* r, int n, const float* u, const float* v, 
   r->n = n;
   r->jb_sel = 0;
   r->last_iters = 0;
+  return HS_OK;
+}
+
+int hs_refiner_set_first_image(hs_refiner* r, hs_image* im, float ab_exposure) {
+  return set_image(r, im, &hs_refiner::d_img1, &hs_refiner::have1, &hs_refiner::expo1, ab_exposure);
+}
+
+int hs_refiner_set_second_image(hs_refiner* r, hs_image* im, float ab_exposure) {
+  return set_image(r, im, &hs_refiner::d_img2, &hs_refiner::have2, &hs_refiner::expo2, ab_exposure);
+}
+
+int hs_refiner_set_points_flow(hs_refiner* r, hs_flow* f, const uint8_t* tri, const float* z) {
+  if (!r || !f || !tri || !z) return hs::fail(HS_ERR_INVALID, "null argument");
+  int dev = 0, w = 0, h = 0, n = 0;
+  const float2* d_first = nullptr;
+  if (!hs_flow_first_points(f, &dev, &w, &h, &n, &d_first))
+    return hs::fail(HS_ERR_STATE, "the flow holds no first frame (hs_flow_set_first)");
+  if (dev != r->device) return hs::fail(HS_ERR_INVALID, "flow and refiner are on different devices");
+  if (w != r->W || h != r->H) return hs::fail(HS_ERR_INVALID, "flow size differs from the refiner's");
+  if (n <= 0) return hs::fail(HS_ERR_INVALID, "the flow's first frame has no points");
+  HS_HIP(hipSetDevice(r->device));
+  hs::Pool scratch;  // freed on every return path
+  uint8_t* d_tri = nullptr;
+  float* d_z = nullptr;
+  int* d_bad = nullptr;
+  HS_TRY(scratch.alloc(&d_tri, (size_t)n));
+  HS_TRY(scratch.alloc(&d_z, (size_t)n));
+  HS_TRY(scratch.alloc_zero(&d_bad, 1, r->stream));
+  HS_TRY(alloc_points(r, n));
+  hipStream_t s = r->stream;
+  HS_HIP(hipMemcpyAsync(d_tri, tri, (size_t)n, hipMemcpyHostToDevice, s));
+  HS_HIP(hipMemcpyAsync(d_z, z, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
+  HsRefPointsArgs a;
+  a.n = n;
+  a.W = r->W;
+  a.H = r->H;
+  a.n_planes = PF_COUNT;
+  a.pl_u = PF_U; a.pl_v = PF_V; a.pl_invz = PF_INVZ; a.pl_id = PF_ID; a.pl_idn = PF_IDN; a.pl_ir = PF_IR;
+  a.first = d_first;
+  a.tri = d_tri;
+  a.z = d_z;
+  a.pf = r->d_pf;
+  a.pb = r->d_pb;
+  a.n_bad = d_bad;
+  hipLaunchKernelGGL(hs_k_ref_points, dim3((n + 255) / 256), dim3(256), 0, s, a);
+  HS_HIP(hipGetLastError());
+  // the one read-back: the keys outside the image (also the wait after which tri / z / the flow's keys are free)
+  HS_HIP(hipMemcpyAsync(&r->h_flags[2], d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  if (r->h_flags[2] != 0) return hs::fail(HS_ERR_INVALID, "keypoint outside the image");  // r->n stays 0: no points
+  r->n = n;
+  r->jb_sel = 0;
+  r->last_iters = 0;
+  return HS_OK;
+}
+
+int hs_refiner_get_videpth(hs_refiner* r, float* videpth) {
+  if (!r || !videpth) return hs::fail(HS_ERR_INVALID, "null");
+  if (r->n <= 0) return hs::fail(HS_ERR_STATE, "no points");
+  HS_HIP(hipSetDevice(r->device));
+  const size_t n = r->n;
+  std::vector<float> id(n), iz(n);
+  std::vector<uint8_t> tri(n), good(n);
+  const HsRefPoints p = points_of(r);
+  HS_HIP(hipMemcpyAsync(id.data(), p.idepth, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipMemcpyAsync(iz.data(), p.invz, n * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipMemcpyAsync(tri.data(), p.tri, n, hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipMemcpyAsync(good.data(), p.good, n, hipMemcpyDeviceToHost, r->stream));
+  HS_HIP(hipStreamSynchronize(r->stream));
+  for (size_t i = 0; i < n; i++) videpth[i] = hs::init_videpth(tri[i] != 0, good[i] != 0, id[i], iz[i]);
+  return HS_OK;
+}
+
+int hs_refiner_seed_ba(hs_refiner* r, hs_ctx* ba, int frame, uint8_t* why_out, int* handles_out, int* n_seeded) {
+  if (!r || !ba) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (ba->comm_lost) return hs::fail(HS_ERR_RCCL, "communicator aborted by an earlier call (a peer rank failed)");
+  if (ba->multi_rank()) return hs::fail(HS_ERR_STATE, "hs_refiner_seed_ba needs a single-rank BA context");
+  if (r->n <= 0) return hs::fail(HS_ERR_STATE, "no points (hs_refiner_set_points / hs_refiner_set_points_flow)");
+  if (!r->have1) return hs::fail(HS_ERR_STATE, "no first frame (hs_refiner_set_first_image / hs_refiner_set_frames)");
+  if (ba->device != r->device) return hs::fail(HS_ERR_INVALID, "refiner and BA context on different devices");
+  if (!ba->d_state || !ba->haveCam) return hs::fail(HS_ERR_STATE, "the BA context has no window");
+  if (ba->cam.width != r->W || ba->cam.height != r->H) return hs::fail(HS_ERR_INVALID, "image size mismatch");
+  HS_TRY(hs::seed_frame_check(ba, frame));
+  HS_HIP(hipSetDevice(r->device));
+  const int n = r->n;
+  if (n > r->seed_cap) {
+    r->seed_cap = 0;
+    HS_TRY(r->pool.alloc(&r->d_why, (size_t)n));
+    HS_TRY(r->pool.pinned(&r->h_why, (size_t)n));
+    if (!r->d_nseed) HS_TRY(r->pool.alloc(&r->d_nseed, 1));
+    r->seed_cap = n;
+  }
+  if (!r->ev_handoff) HS_HIP(hipEventCreateWithFlags(&r->ev_handoff, hipEventDisableTiming));
+  hipStream_t s = r->stream;
+  // the refiner's stream after the BA's: its last commit gathered from the staging array written here
+  HS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
+  HS_HIP(hipStreamWaitEvent(s, ba->ev_ready, 0));
+  const HsRefPoints p = points_of(r);
+  HsInitSeedArgs a;
+  a.n = n;
+  a.W = r->W;
+  a.H = r->H;
+  a.base = ba->n_dev_staged;
+  a.room = std::max(0, ba->cap_P - ba->n_dev_staged);
+  a.img = r->d_img1;
+  a.u = p.u;
+  a.v = p.v;
+  a.invz = p.invz;
+  a.idepth = p.idepth;
+  a.tri = p.tri;
+  a.good = p.good;
+  a.outlierTHSumComponent = ba->P.outlierTHSumComponent;
+  a.priorF = ba->P.idepthFixPrior * 1.0f * 1.0f;  // as hs_ba_insert_points with has_depth_prior
+  a.why = r->d_why;
+  a.n_seeded = r->d_nseed;
+  a.out = ba->d_act_stage;
+  hipLaunchKernelGGL(hs_k_init_seed, dim3(1), dim3(1024), 0, s, a);
+  HS_HIP(hipGetLastError());
+  // the structural read-back: why (n bytes) and the count; the mirror has to learn how many points joined
+  HS_HIP(hipMemcpyAsync(r->h_why, r->d_why, (size_t)n, hipMemcpyDeviceToHost, s));
+  HS_HIP(hipMemcpyAsync(&r->h_flags[1], r->d_nseed, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  const int ns = r->h_flags[1];
+  if (hs::mirror_points(ba) + ns > ba->cap_P || ba->n_dev_staged + ns > ba->cap_P)
+    return hs::fail(HS_ERR_NOMEM, "seeded points exceed the BA context's point capacity (hs_ba_reserve)");
+  HS_TRY(hs::stage_seeded(ba, ns, frame, handles_out));
+  // the BA's commit gathers the staged points: its stream after the refiner's
+  HS_HIP(hipEventRecord(r->ev_handoff, s));
+  HS_HIP(hipStreamWaitEvent(ba->stream, r->ev_handoff, 0));
+  if (why_out) std::memcpy(why_out, r->h_why, (size_t)n);
+  if (n_seeded) *n_seeded = ns;
   return HS_OK;
 }
 

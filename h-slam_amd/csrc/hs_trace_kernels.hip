@@ -1,6 +1,6 @@
 // hs_trace_kernels.hip — ImmaturePoint ctor and traceOn as CDNA4 kernels.
 //
-// hs_k_imm_ctor   one thread per new point: 8 BiLin taps of the host KF (Src/ImmaturePoint.cpp:7-32).
+// hs_k_imm_ctor   one thread per new point: 8 BiLin taps of the host KF (Src/ImmaturePoint.cpp:7-32; hs_imm_ctor.h).
 // hs_k_trace_on   one wave64 per immature point (Src/ImmaturePoint.cpp:40-350):
 //   * the scalar prelude (projection of idepth_min / idepth_max, OOB / SKIPPED / BADCONDITION decisions,
 //     errorInPixel, numSteps, randShift, rotated pattern) is wave-uniform and computed in every lane;
@@ -16,6 +16,7 @@
 #include "hs_trace_kernels.h"
 
 #pragma clang fp contract(off)
+#include "hs_imm_ctor.h"
 #include "hs_interp.h"
 
 namespace {
@@ -23,9 +24,8 @@ namespace {
 using hs_img::clamp_base;
 using hs_img::interp31;
 using hs_img::interp33;
-using hs_img::interp33BiLin;
 
-constexpr int kPat[8][2] = {{0, -2}, {-1, -1}, {1, -1}, {-2, 0}, {0, 0}, {2, 0}, {-1, 1}, {0, 2}};
+using hs_imm::kPat;
 
 // v^T M v with Eigen's evaluation order (row vector first, then the dot product)
 __device__ __forceinline__ float quad2(float g0, float g1, float g2, float g3, float x, float y) {
@@ -49,27 +49,10 @@ __global__ __launch_bounds__(256) void hs_k_imm_ctor(HsImmCtorArgs a) {
   const int h = a.host[p];
   const float4* img = a.host_img[h];
   const float u = a.u[p], v = a.v[p];
-  float col[8], wgt[8];
-  float g0 = 0, g1 = 0, g2 = 0, g3 = 0;
+  float col[8], wgt[8], g[4];
   float eTH = 0, q = 10000;
-  bool bad = false;
-#pragma unroll
-  for (int idx = 0; idx < 8; idx++) {
-    const float3 ptc = interp33BiLin(img, u + kPat[idx][0], v + kPat[idx][1], a.W, a.H);
-    col[idx] = bad ? 0.f : ptc.x;
-    wgt[idx] = 0;
-    if (bad) continue;
-    if (!isfinite(ptc.x)) {  // energyTH = NaN; return (quality left unset: NaN here, as the oracle)
-      bad = true;
-      continue;
-    }
-    g0 = g0 + ptc.y * ptc.y;
-    g1 = g1 + ptc.y * ptc.z;
-    g2 = g2 + ptc.z * ptc.y;
-    g3 = g3 + ptc.z * ptc.z;
-    wgt[idx] = sqrtf(a.outlierTHSumComponent / (a.outlierTHSumComponent + (ptc.y * ptc.y + ptc.z * ptc.z)));
-  }
-  if (bad) {
+  const bool bad = !hs_imm::ctor_point(img, u, v, a.W, a.H, a.outlierTHSumComponent, col, wgt, g);
+  if (bad) {  // energyTH = NaN; return (quality left unset: NaN here, as the oracle)
     eTH = __builtin_nanf("");
     q = __builtin_nanf("");
   } else {
@@ -82,7 +65,7 @@ __global__ __launch_bounds__(256) void hs_k_imm_ctor(HsImmCtorArgs a) {
   c4[1] = make_float4(col[4], col[5], col[6], col[7]);
   w4[0] = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
   w4[1] = make_float4(wgt[4], wgt[5], wgt[6], wgt[7]);
-  reinterpret_cast<float4*>(a.gradH)[p] = make_float4(g0, g1, g2, g3);
+  reinterpret_cast<float4*>(a.gradH)[p] = make_float4(g[0], g[1], g[2], g[3]);
   a.energyTH[p] = eTH;
   a.quality[p] = q;
   a.idepth_min[p] = 0;

@@ -239,6 +239,12 @@ SIGNATURES = {
     "hs_extractor_extract_image": ([VP, VP, VP, VP], I),
     "hs_flow_track_image": ([VP, VP, C.c_float, VP], I),
     "hs_image_to_ba": ([VP, VP, I], I),
+    # include/hs_init.h
+    "hs_refiner_set_first_image": ([VP, VP, C.c_float], I),
+    "hs_refiner_set_second_image": ([VP, VP, C.c_float], I),
+    "hs_refiner_set_points_flow": ([VP, VP, VP, VP], I),
+    "hs_refiner_get_videpth": ([VP, VP], I),
+    "hs_refiner_seed_ba": ([VP, VP, I, VP, VP, VP], I),
 }
 
 _lib = None

@@ -6,6 +6,14 @@ Names follow Include/Initializer.h:108-157 / Src/Initializer.cpp:1330-2270:
     pose, videpth, good = dr.Refine(pose) # Refine + the ctor's _Pose / _videpth write-back
     H, b, Hsc, bsc, res = dr.calcResAndGS(T, aff)   # resetPoints + one calcResAndGS (parity seam)
 
+The initializer hand-off on the device (include/hs_init.h) starts from a refiner without frames or points:
+
+    dr = DirectRefinement.bare(width, height, K4)
+    dr.set_first_image(image, expo)       # hslam_amd.image.DeviceImage, level 0, device to device
+    dr.set_second_image(image, expo)
+    dr.set_points_flow(flow, tri, z)      # mvKeys from the hslam_amd.flow.KeypointFlow's FirstFramePts
+    why, handles = dr.seed_window(ba, 0)  # System::InitFromInitializer's point loop into a hslam_amd.ba.BAWindow
+
 The LM loop runs on the GPU in one workgroup (hs_k_refine); there is no CPU fallback.
 """
 from __future__ import annotations
@@ -30,6 +38,54 @@ class DirectRefinement:
                                              ptr(np.ascontiguousarray(s.img2, np.float32)),
                                              float(s.expo1), float(s.expo2)))
         self.set_points(s.u, s.v, s.tri, s.z)
+
+    @classmethod
+    def bare(cls, width: int, height: int, K4, device: int = 0):
+        """A refiner of this size without frames or points (hs_refiner_create alone)."""
+        self = cls.__new__(cls)
+        self.lib = load()
+        h = C.c_void_p()
+        check(self.lib.hs_refiner_create(C.byref(h), device, int(width), int(height),
+                                         ptr(np.ascontiguousarray(K4, np.float64))))
+        self.h = h
+        self.n = 0
+        return self
+
+    def set_frames(self, img1, img2, expo1: float = 0.0, expo2: float = 0.0):
+        """Both frames from host (h, w, 3) (I, dx, dy) arrays (hs_refiner_set_frames)."""
+        check(self.lib.hs_refiner_set_frames(self.h, ptr(np.ascontiguousarray(img1, np.float32)),
+                                             ptr(np.ascontiguousarray(img2, np.float32)), float(expo1), float(expo2)))
+
+    def set_first_image(self, image, ab_exposure: float = 0.0):
+        """FirstFrame from level 0 of a hslam_amd.image.DeviceImage, device to device; returns without waiting."""
+        check(self.lib.hs_refiner_set_first_image(self.h, image.h, float(ab_exposure)))
+
+    def set_second_image(self, image, ab_exposure: float = 0.0):
+        check(self.lib.hs_refiner_set_second_image(self.h, image.h, float(ab_exposure)))
+
+    def set_points_flow(self, flow, tri, z):
+        """The ctor's Pnt set-up with mvKeys read from the flow's FirstFramePts on the device; tri / z from the host."""
+        t, zz = np.ascontiguousarray(tri, np.uint8), np.ascontiguousarray(z, np.float32)
+        self.n = 0
+        check(self.lib.hs_refiner_set_points_flow(self.h, flow.h, ptr(t), ptr(zz)))
+        self.n = len(t)
+
+    def videpth(self):
+        """Initializer::videpth as InitFromInitializer reads it: -1 untriangulated, the refined idepth where good,
+        1 / z elsewhere."""
+        out = np.zeros(self.n, np.float32)
+        check(self.lib.hs_refiner_get_videpth(self.h, ptr(out)))
+        return out
+
+    def seed_window(self, ba, frame: int):
+        """InitFromInitializer's point loop into window frame `frame` of a hslam_amd.ba.BAWindow, staged on the
+        device.  Returns (why [n] (0 seeded, 1 no depth, 2 non-finite colour, 3 border), the seeded points' handles in
+        mvKeys order); the caller's next makeIDX commits them."""
+        why = np.zeros(self.n, np.uint8)
+        hd = np.zeros(max(self.n, 1), np.int32)
+        ns = C.c_int()
+        check(self.lib.hs_refiner_seed_ba(self.h, ba.h, int(frame), ptr(why), ptr(hd), C.byref(ns)))
+        return why, hd[:ns.value].copy()
 
     def set_points(self, u, v, tri, z):
         cols = [np.ascontiguousarray(u, np.float32), np.ascontiguousarray(v, np.float32),
