@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "hs_ba_ctx.h"
-#include "hs_pyr_kernels.h"
+#include "hs_image_kernels.h"
 
 using namespace hs;
 
@@ -444,7 +444,7 @@ int hs_ba_set_frame_image_raw(hs_ctx* c, int frame, const float* raw) {
   HS_HIP(hipMemcpyAsync(c->d_raw, c->h_raw, sizeof(float) * c->img_px, hipMemcpyHostToDevice, c->stream));
   HS_HIP(hipEventRecord(c->ev_upload, c->stream));
   float4* lv[1] = {dst};
-  HS_HIP(hs_build_dir_pyramid(c->stream, c->d_raw, c->cam.width, c->cam.height, 1, lv, nullptr));
+  HS_HIP(hs_img_build(c->stream, c->cam.width, c->cam.height, 1, lv, nullptr, nullptr, c->d_raw, nullptr));
   return pack_slot(c, c->wframes[frame].slot);
 }
 

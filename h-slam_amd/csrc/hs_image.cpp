@@ -1,6 +1,7 @@
-// hs_image.cpp — the image context of include/hs_image.h: argument checks, the staging of the raw frame, one set as
-// an upload and two launches on the image's stream, and the two events that order it with its consumers (the
-// consumers' entries live in each consumer's own .cpp).
+// hs_image.cpp — the launcher of the library's pyramid build (hs_img_build: the image's sets and every context's own
+// frame go through it), and the image context of include/hs_image.h: argument checks, the staging of the raw frame,
+// one set as an upload and two launches on the image's stream, and the two events that order it with its consumers
+// (the consumers' entries live in each consumer's own .cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -11,7 +12,6 @@
 #include "../../include/hs_image.h"
 #include "hs_host.h"
 #include "hs_image_kernels.h"
-#include "hs_pyr_kernels.h"
 #include "hs_undist_kernels.h"
 
 struct hs_image : hs::Device {  // e0, e1: the last set's first and last kernel; e1 is also its "ready" event
@@ -21,7 +21,7 @@ struct hs_image : hs::Device {  // e0, e1: the last set's first and last kernel;
   float* d_absg[HS_MAX_LEVELS] = {nullptr};   // absSquaredGrad[l]
   uint8_t* d_img8 = nullptr;                  // cvImgL
   // staging of the caller's frame: pinned on the host (a set returns before its upload ran), then on the device;
-  // the undistorter's own d_in belongs to the stream of whoever calls hs_undist_enqueue
+  // the undistorter's own d_in belongs to the stream of whoever calls hs_undist_upload
   uint8_t *h_raw = nullptr, *d_raw = nullptr;
   size_t raw_cap = 0;
   float *h_fimg = nullptr, *d_fimg = nullptr;
@@ -49,37 +49,55 @@ int begin_set(hs_image* im) {
   return HS_OK;
 }
 
-// the two kernels, between the timing events; a.fimg or a.raw (and the tables) are set by the caller
-int run_set(hs_image* im, HsImgLevelsArgs& a) {
-  hipStream_t s = im->stream;
-  a.W = im->W;
-  a.H = im->H;
-  a.nlev = im->nlev;
-  HsImgGradsArgs g;
-  g.nlev = im->nlev;
-  int blocks = 0;
-  for (int l = 0; l < HS_MAX_LEVELS; l++) {
-    const bool on = l < im->nlev;
-    a.lvl[l] = on ? im->d_lvl[l] : nullptr;
-    g.lvl[l] = a.lvl[l];
-    g.absg[l] = on ? im->d_absg[l] : nullptr;
-    g.w[l] = on ? im->W >> l : 0;
-    g.h[l] = on ? im->H >> l : 0;
-    g.boff[l] = blocks;
-    blocks += (g.w[l] * g.h[l] + 255) / 256;
-  }
-  g.boff[HS_MAX_LEVELS] = blocks;
-  HS_HIP(hipEventRecord(im->e0, s));
-  hipLaunchKernelGGL(hs_k_img_levels, dim3((im->W + kImgTile - 1) / kImgTile, (im->H + kImgTile - 1) / kImgTile),
-                     dim3(kImgThreads), 0, s, a);
-  HS_HIP(hipGetLastError());
-  hipLaunchKernelGGL(hs_k_img_grads, dim3(blocks), dim3(256), 0, s, g);
-  HS_HIP(hipGetLastError());
-  HS_HIP(hipEventRecord(im->e1, s));
+// the build of every level from the staged frame (fimg, or u8 with its tables), between the timing events
+int run_set(hs_image* im, uint8_t* img8, const float* fimg, const HsUndistArgs* u8) {
+  HS_HIP(hipEventRecord(im->e0, im->stream));
+  HS_HIP(hs_img_build(im->stream, im->W, im->H, im->nlev, im->d_lvl, im->d_absg, img8, fimg, u8));
+  HS_HIP(hipEventRecord(im->e1, im->stream));
   return HS_OK;
 }
 
 }  // namespace
+
+hipError_t hs_img_build(hipStream_t stream, int W, int H, int nlev, float4* const* lvl, float* const* absg,
+                        uint8_t* img8, const float* fimg, const HsUndistArgs* u8) {
+  const int first = (fimg || u8) ? 0 : 1;  // the first level whose gradients are formed here
+  if (first >= nlev) return hipSuccess;
+  HsImgLevelsArgs a;
+  a.W = W;
+  a.H = H;
+  a.nlev = nlev;
+  a.w_in = u8 ? u8->w_in : 0;
+  a.h_in = u8 ? u8->h_in : 0;
+  a.passthrough = u8 ? u8->passthrough : 0;
+  a.fimg = fimg;
+  a.raw = (u8 && !fimg) ? u8->raw : nullptr;
+  a.map = u8 ? u8->map : nullptr;
+  a.Binv = u8 ? u8->Binv : nullptr;
+  a.B = u8 ? u8->B : nullptr;
+  a.vinv = u8 ? u8->vinv : nullptr;
+  a.img8 = a.raw ? img8 : nullptr;
+  HsImgGradsArgs g;
+  g.nlev = nlev;
+  int blocks = 0;
+  for (int l = 0; l < HS_MAX_LEVELS; l++) {
+    const bool on = l < nlev;
+    a.lvl[l] = on ? lvl[l] : nullptr;
+    g.lvl[l] = a.lvl[l];
+    g.absg[l] = (on && absg) ? absg[l] : nullptr;
+    g.w[l] = (on && l >= first) ? W >> l : 0;  // a level below `first` gets no blocks
+    g.h[l] = (on && l >= first) ? H >> l : 0;
+    g.boff[l] = blocks;
+    blocks += (g.w[l] * g.h[l] + 255) / 256;
+  }
+  g.boff[HS_MAX_LEVELS] = blocks;
+  hipLaunchKernelGGL(hs_k_img_levels, dim3((W + kImgTile - 1) / kImgTile, (H + kImgTile - 1) / kImgTile),
+                     dim3(kImgThreads), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hs_k_img_grads, dim3(blocks), dim3(256), 0, stream, g);
+  return hipGetLastError();
+}
 
 int hs_image_view(hs_image* im, int device, int w, int h, int min_levels, bool need_img8, HsImageView* v) {
   if (!im) return hs::fail(HS_ERR_INVALID, "null image");
@@ -176,19 +194,9 @@ int hs_image_set_u8(hs_image* im, hs_undistorter* u, const uint8_t* raw) {
   HS_HIP(hipMemcpyAsync(im->d_raw, im->h_raw, n_in, hipMemcpyHostToDevice, im->stream));
   HS_HIP(hipEventRecord(im->ev_upload, im->stream));
   im->upload_pending = true;
-  HsImgLevelsArgs a;
-  a.w_in = t.w_in;
-  a.h_in = t.h_in;
-  a.passthrough = t.passthrough;
-  a.fimg = nullptr;
-  a.raw = im->d_raw;
-  a.map = t.map;
-  a.Binv = t.Binv;
-  a.B = t.B;
-  a.vinv = t.vinv;
-  a.img8 = im->d_img8;
+  t.raw = im->d_raw;  // the image's own staging, on its own stream
   im->have = im->have_img8 = false;  // until the launches are enqueued
-  HS_TRY(run_set(im, a));
+  HS_TRY(run_set(im, im->d_img8, nullptr, &t));
   im->have = im->have_img8 = true;
   return HS_OK;
 }
@@ -205,43 +213,9 @@ int hs_image_set_raw(hs_image* im, const float* fimg) {
   HS_HIP(hipMemcpyAsync(im->d_fimg, im->h_fimg, n * sizeof(float), hipMemcpyHostToDevice, im->stream));
   HS_HIP(hipEventRecord(im->ev_upload, im->stream));
   im->upload_pending = true;
-  HsImgLevelsArgs a;
-  a.w_in = a.h_in = 0;
-  a.passthrough = 0;
-  a.fimg = im->d_fimg;
-  a.raw = nullptr;
-  a.map = nullptr;
-  a.Binv = a.B = a.vinv = nullptr;
-  a.img8 = nullptr;
   im->have = im->have_img8 = false;
-  HS_TRY(run_set(im, a));
+  HS_TRY(run_set(im, nullptr, im->d_fimg, nullptr));
   im->have = true;
-  return HS_OK;
-}
-
-int hs_image_time_chain(hs_image* im, hs_undistorter* u, const uint8_t* raw, double* ms) {
-  if (!im || !u || !raw || !ms) return hs::fail(HS_ERR_INVALID, "null argument");
-  HS_TRY(hs_undist_match(u, im->device, im->W, im->H));
-  HS_TRY(begin_set(im));
-  if (!im->d_fimg) {
-    HS_TRY(im->pool.pinned(&im->h_fimg, (size_t)im->W * im->H));
-    HS_TRY(im->pool.alloc(&im->d_fimg, (size_t)im->W * im->H));
-  }
-  hipStream_t s = im->stream;
-  im->have = im->have_img8 = false;
-  // the undistorter's own staging: this entry waits before it returns, as every caller of hs_undist_enqueue does
-  hipError_t e = hs_undist_enqueue(u, s, raw, nullptr, nullptr);  // the upload (and an untimed launch without outputs)
-  if (e == hipSuccess) e = hipEventRecord(im->e0, s);
-  if (e == hipSuccess) e = hs_undist_enqueue(u, s, nullptr, im->d_fimg, im->d_img8);
-  if (e == hipSuccess) e = hs_build_dir_pyramid(s, im->d_fimg, im->W, im->H, im->nlev, im->d_lvl, im->d_absg);
-  if (e == hipSuccess) e = hipEventRecord(im->e1, s);
-  const hipError_t es = hipStreamSynchronize(s);  // also after a failure: raw is the caller's
-  if (e == hipSuccess) e = es;
-  float f = 0;
-  if (e == hipSuccess) e = hipEventElapsedTime(&f, im->e0, im->e1);
-  if (e != hipSuccess) return hs::fail(HS_ERR_HIP, std::string("hs_image_time_chain: ") + hipGetErrorString(e));
-  im->have = im->have_img8 = true;
-  *ms = f;
   return HS_OK;
 }
 

@@ -1,52 +1,31 @@
-// hs_image_kernels.hip — one camera frame into every level of its direct-image pyramid in two launches
-// (include/hs_image.h), in place of the 2L+1 of hs_undist_enqueue + hs_build_dir_pyramid, and bit-identical to them:
+// hs_image_kernels.hip — Frame::CreateDirPyrs (Src/Frame.cpp:104-181) on the device: every level of a frame's
+// direct-image pyramid (I, dI/dx, dI/dy), absSquaredGrad and cvImgL in two launches.  The library's one pyramid
+// implementation: hs_img_build (hs_image.cpp) launches it for the device image and for every context's own frame.
 //   hs_k_img_levels  one workgroup per 32 x 32 tile of level 0.  A thread forms the level-0 intensity of 4 of the
-//                    tile's pixels -- hs_k_undistort's arithmetic (include/hs_undist.h: the same taps, weights and
-//                    unfused left-to-right sum, the same img8) or a plain load of the float frame -- writes the texel
-//                    (I, 0, 0, 0) and cvImgL and keeps I in LDS; the workgroup then folds the tile into levels
-//                    1..L-1 in LDS, 0.25f * (((tl + tr) + bl) + br) as hs_k_pyr_down, writing each level's texels as
-//                    it goes.  A pixel exists at level l iff x < W >> l and y < H >> l; its four sources then exist at
-//                    level l-1 and, the tile's side being a multiple of 2^(L-1), lie in the same tile.  Pixels that do
-//                    not exist (partial tiles at the right and bottom, the odd last column / row of a level) are
-//                    computed from whatever their sources hold and never stored.
-//   hs_k_img_grads   hs_k_pyr_grad's arithmetic over the texels of all levels in one grid (a workgroup belongs to
-//                    one level).  A separate launch: it reads the neighbours' intensities, which other workgroups of
-//                    hs_k_img_levels wrote.
+//                    tile's pixels -- a plain load of the float frame (ImageData::fImgL), or the undistorted pixel of
+//                    a raw u8 frame (hs_undist_px.h, the arithmetic of hs_k_undistort, with its img8) -- writes the
+//                    texel (I, 0, 0, 0) and cvImgL and keeps I in LDS; with neither source it reads I from the level-0
+//                    texel already in place and leaves that level alone.  The workgroup then folds the tile into
+//                    levels 1..L-1 in LDS, 0.25f * (((tl + tr) + bl) + br) in the reference's operation order,
+//                    writing each level's texels as it goes.  A pixel exists at level l iff x < W >> l and y < H >> l
+//                    (CalibData's wpyr / hpyr rule); its four sources then exist at level l-1 and, the tile's side
+//                    being a multiple of 2^(L-1), lie in the same tile.  Pixels that do not exist (partial tiles at
+//                    the right and bottom, the odd last column / row of a level) are computed from whatever their
+//                    sources hold and never stored.
+//   hs_k_img_grads   central differences over the interior index range [w, w*(h-1)) of each level (row-wrapped at the
+//                    left / right columns exactly as the reference's linear index loop), non-finite -> 0, and
+//                    absSquaredGrad = dx*dx + dy*dy (the gamma weighting is skipped: Calib->PhotoUnDistL is null,
+//                    SURVEY.md Appendix B quirk 4).  The first and last rows keep dI = 0 (the reference leaves them
+//                    uninitialised).  All levels in one grid (a workgroup belongs to one level); a level the launcher
+//                    gives no blocks (those below its first level) is never selected.  A separate launch: it reads
+//                    the neighbours' intensities, which other workgroups of hs_k_img_levels wrote.
 // Latency-bound, not bandwidth-bound (a 640 x 480 frame moves ~7 MB): what the fusion saves is launches.
 #include "hs_image_kernels.h"
+#include "hs_undist_px.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-// cv::saturate_cast<uchar>(float): round half to even, clamped to 0..255
-__device__ __forceinline__ int sat8(float v) {
-  const int r = __float2int_rn(v);
-  return r < 0 ? 0 : (r > 255 ? 255 : r);
-}
-
-// hs_k_undistort's value of output pixel i
-__device__ __forceinline__ float undistort_px(const HsImgLevelsArgs& a, const float* sBinv, int i) {
-  auto tap = [&](int j) -> float {
-    const int p = a.raw[j];
-    float v = a.Binv ? sBinv[p] : (float)p;
-    if (a.vinv) v = v * a.vinv[j];
-    return v;
-  };
-  if (a.passthrough) return tap(i);
-  const int2 s = a.map[i];
-  const int ix = s.x >> 5, iy = s.y >> 5;
-  const float fx = (float)(s.x & 31) * (1.f / 32), fy = (float)(s.y & 31) * (1.f / 32);
-  const float w0 = (1.f - fy) * (1.f - fx), w1 = (1.f - fy) * fx, w2 = fy * (1.f - fx), w3 = fy * fx;
-  const bool x0 = ix >= 0 && ix < a.w_in, x1 = ix + 1 >= 0 && ix + 1 < a.w_in;
-  const bool y0 = iy >= 0 && iy < a.h_in, y1 = iy + 1 >= 0 && iy + 1 < a.h_in;
-  const int j = iy * a.w_in + ix;
-  const float s00 = (x0 && y0) ? tap(j) : 0.f;
-  const float s01 = (x1 && y0) ? tap(j + 1) : 0.f;
-  const float s10 = (x0 && y1) ? tap(j + a.w_in) : 0.f;
-  const float s11 = (x1 && y1) ? tap(j + a.w_in + 1) : 0.f;
-  return s00 * w0 + s01 * w1 + s10 * w2 + s11 * w3;
-}
-
 // LDS offset of level l's (kImgTile >> l)^2 block: 0, 1024, 1280, 1344, 1360, 1364
 constexpr int lds_off(int l) {
   int o = 0;
@@ -61,7 +40,7 @@ __global__ __launch_bounds__(kImgThreads) void hs_k_img_levels(HsImgLevelsArgs a
   __shared__ float sI[lds_off(HS_MAX_LEVELS)];
   static_assert(kImgThreads == 256 && kImgTile == 32, "a thread per table entry, 8 tile rows per pass");
   const int t = threadIdx.x;
-  if (!a.fimg) {
+  if (a.raw) {
     if (a.Binv) sBinv[t] = a.Binv[t];
     if (a.B) sB[t] = a.B[t];
     __syncthreads();
@@ -75,9 +54,14 @@ __global__ __launch_bounds__(kImgThreads) void hs_k_img_levels(HsImgLevelsArgs a
     float f = 0.f;
     if (x < a.W && y < a.H) {
       const int i = y * a.W + x;
-      f = a.fimg ? a.fimg[i] : undistort_px(a, sBinv, i);
-      a.lvl[0][i] = make_float4(f, 0.f, 0.f, 0.f);
-      if (a.img8) a.img8[i] = (uint8_t)(a.B ? sat8(sB[sat8(f)]) : sat8(f));
+      if (a.fimg || a.raw) {
+        f = a.fimg ? a.fimg[i]
+                   : undistort_px(a.raw, sBinv, a.Binv != nullptr, a.vinv, a.map, a.w_in, a.h_in, a.passthrough, i);
+        a.lvl[0][i] = make_float4(f, 0.f, 0.f, 0.f);
+        if (a.img8) a.img8[i] = (uint8_t)(a.B ? sat8(sB[sat8(f)]) : sat8(f));
+      } else {
+        f = a.lvl[0][i].x;  // level 0 in place: its gradient lanes are the owner's
+      }
     }
     sI[ly * kImgTile + tx] = f;
   }
@@ -130,5 +114,5 @@ __global__ __launch_bounds__(256) void hs_k_img_grads(HsImgGradsArgs a) {
   // threads read the neighbours' intensity lanes and write only their own gradient lanes (no overlap)
   reinterpret_cast<float*>(lvl + i)[1] = dx;
   reinterpret_cast<float*>(lvl + i)[2] = dy;
-  absg[i] = g;
+  if (absg) absg[i] = g;
 }

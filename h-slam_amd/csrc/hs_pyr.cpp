@@ -1,4 +1,4 @@
-// hs_pyr.cpp — host launcher of the device image pyramid and the standalone C-ABI entry (include/hs_pyr.h).
+// hs_pyr.cpp — the standalone C-ABI entry of the device image pyramid (include/hs_pyr.h).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -7,40 +7,7 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_pyr.h"
 #include "hs_host.h"
-#include "hs_pyr_kernels.h"
-
-hipError_t hs_build_dir_pyramid(hipStream_t stream, const float* d_img, int W, int H, int nlev, float4* const* d_lvl,
-                                float* const* d_absg) {
-  const int n0 = W * H;
-  hipLaunchKernelGGL(hs_k_pyr_load, dim3((n0 + 255) / 256), dim3(256), 0, stream, n0, d_img, d_lvl[0]);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  for (int l = 0; l < nlev; l++) {
-    const int wl = W >> l, hl = H >> l, n = wl * hl;
-    if (l > 0) {
-      hipLaunchKernelGGL(hs_k_pyr_down, dim3((n + 255) / 256), dim3(256), 0, stream, wl, hl, W >> (l - 1), d_lvl[l - 1],
-                         d_lvl[l]);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(hs_k_pyr_grad, dim3((n + 255) / 256), dim3(256), 0, stream, wl, hl, d_lvl[l],
-                       d_absg ? d_absg[l] : nullptr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-hipError_t hs_build_dir_pyramid_upper(hipStream_t stream, int W, int H, int nlev, float4* const* d_lvl) {
-  hipError_t e = hipSuccess;
-  for (int l = 1; l < nlev; l++) {
-    const int wl = W >> l, hl = H >> l, n = wl * hl;
-    hipLaunchKernelGGL(hs_k_pyr_down, dim3((n + 255) / 256), dim3(256), 0, stream, wl, hl, W >> (l - 1), d_lvl[l - 1],
-                       d_lvl[l]);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(hs_k_pyr_grad, dim3((n + 255) / 256), dim3(256), 0, stream, wl, hl, d_lvl[l], nullptr);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return e;
-}
+#include "hs_image_kernels.h"
 
 // the body of hs_dir_pyramid; the caller waits for the stream and frees `scratch` on every path
 static int dir_pyramid(hs::Device& dev, hs::Pool& scratch, int device_id, int width, int height, int n_levels,
@@ -57,7 +24,7 @@ static int dir_pyramid(hs::Device& dev, hs::Pool& scratch, int device_id, int wi
     HS_TRY(scratch.alloc(&ag[l], n));
   }
   HS_HIP(hipMemcpyAsync(d_img, img, sizeof(float) * width * height, hipMemcpyHostToDevice, s));
-  HS_HIP(hs_build_dir_pyramid(s, d_img, width, height, n_levels, lv, ag));
+  HS_HIP(hs_img_build(s, width, height, n_levels, lv, ag, nullptr, d_img, nullptr));
   size_t off3 = 0, off1 = 0;
   std::vector<float4> tex;
   for (int l = 0; l < n_levels; l++) {

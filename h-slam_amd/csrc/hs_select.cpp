@@ -12,7 +12,6 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_select.h"
 #include "hs_host.h"
-#include "hs_pyr_kernels.h"
 #include "hs_sel_kernels.h"
 #include "../../include/hs_image.h"
 #include "hs_image_kernels.h"
@@ -282,7 +281,7 @@ extern "C" int hs_selector_make_maps_raw(hs_selector* s, int frame_id, const flo
   const size_t area = (size_t)s->W * s->H;
   HS_HIP(hipMemcpyAsync(s->d_raw, img, area * sizeof(float), hipMemcpyHostToDevice, s->stream));
   HS_HIP(hipEventRecord(s->e0, s->stream));
-  HS_HIP(hs_build_dir_pyramid(s->stream, s->d_raw, s->W, s->H, 3, s->d_lvl, s->d_g));
+  HS_HIP(hs_img_build(s->stream, s->W, s->H, 3, s->d_lvl, s->d_g, nullptr, s->d_raw, nullptr));
   s->last_passes = 0;
   s->have_map = false;
   int n = 0;

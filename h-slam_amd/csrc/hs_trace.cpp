@@ -15,7 +15,6 @@
 #include "hs_ba_ctx.h"
 #include "hs_host.h"
 #include "hs_trace_kernels.h"
-#include "hs_pyr_kernels.h"
 #include "../../include/hs_undist.h"
 #include "hs_undist_kernels.h"
 #include "../../include/hs_extract.h"
@@ -303,7 +302,7 @@ int hs_tracer_set_frame_raw(hs_tracer* t, const float* img) {
   if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
   HS_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
   float4* lv[1] = {t->d_new};
-  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
+  HS_HIP(hs_img_build(t->stream, t->W, t->H, 1, lv, nullptr, nullptr, t->d_raw, nullptr));
   HS_HIP(hipStreamSynchronize(t->stream));
   t->have_frame = true;
   return HS_OK;
@@ -313,10 +312,11 @@ int hs_tracer_set_frame_u8(hs_tracer* t, hs_undistorter* u, const uint8_t* raw) 
   if (!t || !u || !raw) return hs::fail(HS_ERR_INVALID, "null argument");
   HS_TRY(hs_undist_match(u, t->device, t->W, t->H));
   HS_HIP(hipSetDevice(t->device));
-  if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
-  HS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
+  HsUndistArgs tab;
+  hs_undist_tables(u, &tab);
+  HS_HIP(hs_undist_upload(u, t->stream, raw));
   float4* lv[1] = {t->d_new};
-  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, 1, lv, nullptr));
+  HS_HIP(hs_img_build(t->stream, t->W, t->H, 1, lv, nullptr, nullptr, nullptr, &tab));
   HS_HIP(hipStreamSynchronize(t->stream));
   t->have_frame = true;
   return HS_OK;

@@ -14,7 +14,6 @@
 #include "../../include/hs_track.h"
 #include "hs_ba_ctx.h"
 #include "hs_track_kernels.h"
-#include "hs_pyr_kernels.h"
 #include "../../include/hs_undist.h"
 #include "hs_undist_kernels.h"
 #include "../../include/hs_image.h"
@@ -513,8 +512,8 @@ int hs_tracker_set_ref_ba(hs_tracker* t, hs_ctx* ba, int promote_frame, float ab
   if (promote_frame) {
     for (int l = 0; l < t->nlev; l++) std::swap(t->d_ref[l], t->d_new[l]);
     t->haveFrame = false;  // d_new now holds the old reference: the next frame to track must be set
-  } else {
-    HS_HIP(hs_build_dir_pyramid_upper(t->stream, t->W, t->H, t->nlev, t->d_ref));
+  } else {  // no source: level 0 is in place, levels 1.. are built from it
+    HS_HIP(hs_img_build(t->stream, t->W, t->H, t->nlev, t->d_ref, nullptr, nullptr, nullptr, nullptr));
   }
   t->refExposure = ab_exposure;
   t->refAff[0] = aff_g2l[0];
@@ -598,7 +597,7 @@ int hs_tracker_set_frame_raw(hs_tracker* t, const float* img, float ab_exposure)
   HS_HIP(hipSetDevice(t->device));
   if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
   HS_HIP(hipMemcpyAsync(t->d_raw, img, sizeof(float) * t->W * t->H, hipMemcpyHostToDevice, t->stream));
-  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
+  HS_HIP(hs_img_build(t->stream, t->W, t->H, t->nlev, t->d_new, nullptr, nullptr, t->d_raw, nullptr));
   HS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
   t->newExposure = ab_exposure;
   t->haveFrame = true;
@@ -609,9 +608,10 @@ int hs_tracker_set_frame_u8(hs_tracker* t, hs_undistorter* u, const uint8_t* raw
   if (!t || !u || !raw) return hs::fail(HS_ERR_INVALID, "null argument");
   HS_TRY(hs_undist_match(u, t->device, t->W, t->H));
   HS_HIP(hipSetDevice(t->device));
-  if (!t->d_raw) HS_TRY(t->pool.alloc(&t->d_raw, (size_t)t->W * t->H));
-  HS_HIP(hs_undist_enqueue(u, t->stream, raw, t->d_raw, nullptr));
-  HS_HIP(hs_build_dir_pyramid(t->stream, t->d_raw, t->W, t->H, t->nlev, t->d_new, nullptr));
+  HsUndistArgs tab;
+  hs_undist_tables(u, &tab);
+  HS_HIP(hs_undist_upload(u, t->stream, raw));
+  HS_HIP(hs_img_build(t->stream, t->W, t->H, t->nlev, t->d_new, nullptr, nullptr, nullptr, &tab));
   HS_HIP(hipStreamSynchronize(t->stream));  // the caller's buffer may go away after return
   t->newExposure = ab_exposure;
   t->haveFrame = true;

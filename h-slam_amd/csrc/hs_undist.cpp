@@ -1,5 +1,5 @@
 // hs_undist.cpp — the undistorter context of include/hs_undist.h: the host tables (hs_undist_tables.cpp) placed on
-// the device, the standalone apply and the launcher the tracker and the tracer chain in front of their pyramid.
+// the device, the standalone apply, and the staging and launcher the other contexts' _u8 entries use.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,7 +49,7 @@ void hs_undist_tables(const hs_undistorter* u, HsUndistArgs* a) {
   a->h_in = u->h_in;
   a->n_out = u->w_out * u->h_out;
   a->passthrough = u->passthrough ? 1 : 0;
-  a->raw = nullptr;
+  a->raw = u->d_in;
   a->map = u->d_map;
   a->Binv = u->have_gamma ? u->d_Binv : nullptr;
   a->B = (u->have_gamma || u->have_vig) ? u->d_B : nullptr;
@@ -58,16 +58,18 @@ void hs_undist_tables(const hs_undistorter* u, HsUndistArgs* a) {
   a->img8 = nullptr;
 }
 
+hipError_t hs_undist_upload(hs_undistorter* u, hipStream_t stream, const uint8_t* raw) {
+  return hipMemcpyAsync(u->d_in, raw, (size_t)u->w_in * u->h_in, hipMemcpyHostToDevice, stream);
+}
+
 hipError_t hs_undist_enqueue(hs_undistorter* u, hipStream_t stream, const uint8_t* raw, float* d_fimg,
                              uint8_t* d_img8) {
-  const size_t n_in = (size_t)u->w_in * u->h_in;
   if (raw) {  // null: the frame already in the staging (the timing loop)
-    hipError_t e = hipMemcpyAsync(u->d_in, raw, n_in, hipMemcpyHostToDevice, stream);
+    hipError_t e = hs_undist_upload(u, stream, raw);
     if (e != hipSuccess) return e;
   }
   HsUndistArgs a;
   hs_undist_tables(u, &a);
-  a.raw = u->d_in;
   a.fimg = d_fimg;
   a.img8 = d_img8;
   hipLaunchKernelGGL(hs_k_undistort, dim3((a.n_out + 255) / 256), dim3(256), 0, stream, a);

@@ -231,7 +231,6 @@ SIGNATURES = {
     "hs_image_set_raw": ([VP, VP], I),
     "hs_image_get": ([VP, I, VP, VP, VP], I),
     "hs_image_last_stats": ([VP, VP], I),
-    "hs_image_time_chain": ([VP, VP, VP, VP], I),
     "hs_tracker_set_frame_image": ([VP, VP, C.c_float], I),
     "hs_tracer_set_frame_image": ([VP, VP], I),
     "hs_tracer_set_host_image_from": ([VP, I, VP], I),

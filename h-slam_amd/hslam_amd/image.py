@@ -61,14 +61,6 @@ class DeviceImage:
         check(self.lib.hs_image_get(self.h, int(lvl), ptr(d), ptr(g), ptr(c)))
         return (d, g, c) if img8 else (d, g)
 
-    def time_chain(self, undistorter, raw) -> float:
-        """Measurement: the same frame through the launchers set_u8 replaces; their device milliseconds."""
-        a = np.ascontiguousarray(raw, np.uint8)
-        assert a.shape == (undistorter.h_in, undistorter.w_in)
-        ms = C.c_double()
-        check(self.lib.hs_image_time_chain(self.h, undistorter.h, ptr(a), C.byref(ms)))
-        return ms.value
-
     def last_stats(self) -> float:
         """Device milliseconds of the last set's kernels."""
         ms = C.c_double()

@@ -65,11 +65,6 @@ int hs_image_get(hs_image* im, int lvl, float* dirpyr_out, float* absg_out, uint
    that set. */
 int hs_image_last_stats(hs_image* im, double* ms);
 
-/* Measurement (tools/image_time.py): the same frame through the launchers hs_image_set_u8 replaces -- the
-   undistortion kernel, then the 2L launches of the pyramid -- on the image's stream, into the image's own levels;
-   *ms = their device time between one pair of events.  Waits; the image then holds the frame as after a set. */
-int hs_image_time_chain(hs_image* im, hs_undistorter* u, const uint8_t* raw, double* ms);
-
 /* The consumers.  Every entry first checks, before any device call: the image is on the consumer's device and of
    its size and has the levels the consumer reads (HS_ERR_INVALID), and it holds a frame -- with a cvImgL where the
    consumer reads one (HS_ERR_STATE).  A failed entry changes nothing in the consumer. */

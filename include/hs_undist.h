@@ -84,10 +84,10 @@ int hs_undistorter_apply(hs_undistorter* u, const uint8_t* raw, float* fimg_out,
    launches of the kernel (fImg only) between one pair of device events; *ms_per_launch = elapsed / launches. */
 int hs_undistorter_time_kernel(hs_undistorter* u, const uint8_t* raw, int warmup, int launches, float* ms_per_launch);
 
-/* The frame to track / to trace on as the camera's raw u8 frame: w_in*h_in bytes are uploaded, undistorted on the
-   consumer's own stream into its raw staging buffer, and its pyramid is built from there (hs_tracker_set_frame_raw,
-   hs_tracer_set_frame_raw).  The undistorter must be on the consumer's device and its output size the consumer's
-   size, else HS_ERR_INVALID. */
+/* The frame to track / to trace on as the camera's raw u8 frame: w_in*h_in bytes are uploaded on the consumer's own
+   stream, and the consumer's pyramid is built from them, each level-0 pixel undistorted as it is written (the result
+   is that of hs_undistorter_apply followed by hs_tracker_set_frame_raw / hs_tracer_set_frame_raw).  The undistorter
+   must be on the consumer's device and its output size the consumer's size, else HS_ERR_INVALID. */
 int hs_tracker_set_frame_u8(hs_tracker* t, hs_undistorter* u, const uint8_t* raw, float ab_exposure);
 int hs_tracer_set_frame_u8(hs_tracer* t, hs_undistorter* u, const uint8_t* raw);
 

@@ -86,10 +86,10 @@ def test_odd_size_crop():
     im = DeviceImage(c["w_out"], c["h_out"], 3)
     im.set_u8(u, raw)
     check_levels(im, fimg, img8)
-    # the measurement entry runs the launchers the set replaces into the same levels
+    # a second frame into the same levels
     raw2 = np.ascontiguousarray(raw[::-1])
     fimg2, img82 = u.undistort(raw2)
-    assert im.time_chain(u, raw2) > 0
+    im.set_u8(u, raw2)
     check_levels(im, fimg2, img82)
     im.close()
     u.close()

@@ -5,7 +5,7 @@ import ctypes as C
 import pytest
 
 ENTRIES = ("hs_image_create", "hs_image_destroy", "hs_image_set_u8", "hs_image_set_raw", "hs_image_get",
-           "hs_image_last_stats", "hs_image_time_chain", "hs_tracker_set_frame_image", "hs_tracer_set_frame_image",
+           "hs_image_last_stats", "hs_tracker_set_frame_image", "hs_tracer_set_frame_image",
            "hs_tracer_set_host_image_from", "hs_selector_make_maps_image", "hs_extractor_extract_image",
            "hs_flow_track_image", "hs_image_to_ba")
 

@@ -33,16 +33,57 @@ def test_oracle_nonfinite_gradients_are_zero():
     assert np.all(np.isfinite(p[0][..., 1:])) and np.isinf(p[0][5, 6, 0])
 
 
+# (width, height, levels): the smallest shapes at which the build's 32 x 32 tiling can go wrong
+TILE_SHAPES = [(4, 4, 1),      # the smallest legal frame: one partial tile, no fold
+               (5, 7, 2),      # odd sides in one partial tile: the unused last column and row
+               (33, 31, 3),    # a second tile that is one pixel wide, and a bottom row cut one short
+               (64, 64, 6),    # HS_MAX_LEVELS: the fold down to one pixel per tile, a 2 x 2 top level
+               (97, 65, 6)]    # partial tiles at every level, top level 3 x 2
+
+
+def tile_images():
+    """(name, image, levels) of the small cases: seeded random floats in [0, 255], and the non-finite pixel."""
+    out = []
+    for w, h, levels in TILE_SHAPES:
+        rng = np.random.default_rng(1000 * w + h)
+        out.append((f"{w}x{h}x{levels}", rng.uniform(0.0, 255.0, size=(h, w)).astype(np.float32), levels))
+    img = np.full((16, 24), 7.0, np.float32)
+    img[5, 6] = np.inf
+    out.append(("24x16x2 inf", img, 2))
+    return out
+
+
+def test_oracle_small_shapes():
+    """The oracle half of the small device cases: level sizes, zero first / last rows, the non-finite rule."""
+    from oracle_ffi import dir_pyramid
+    for name, img, levels in tile_images():
+        h, w = img.shape
+        p, g = dir_pyramid(img, levels)
+        assert np.array_equal(p[0][..., 0], img), name
+        for l in range(levels):
+            assert p[l].shape == (h >> l, w >> l, 3) and g[l].shape == (h >> l, w >> l), (name, l)
+            assert not p[l][0, :, 1:].any() and not p[l][-1, :, 1:].any(), (name, l)
+            assert np.all(np.isfinite(p[l][..., 1:])) and np.all(np.isfinite(g[l])), (name, l)
+            if l > 0:
+                s = p[l - 1][..., 0]
+                hl, wl = h >> l, w >> l
+                q = np.float32(0.25) * (((s[0:2 * hl:2, 0:2 * wl:2] + s[0:2 * hl:2, 1:2 * wl:2]) +
+                                         s[1:2 * hl:2, 0:2 * wl:2]) + s[1:2 * hl:2, 1:2 * wl:2])
+                assert np.array_equal(p[l][..., 0], q), (name, l)
+
+
 @pytest.mark.gpu
 def test_device_pyramid_bit_exact(raw):
     from hslam_amd.pyr import dir_pyramid as dev
     from oracle_ffi import dir_pyramid
-    for img in (raw.new_pyr[0][..., 0], raw.ref_pyr[0][..., 0]):
-        pg, gg = dev(img, 4)
-        po, go = dir_pyramid(img, 4)
-        for l in range(4):
-            assert np.array_equal(pg[l], po[l]), l
-            assert np.array_equal(gg[l], go[l]), l
+    cases = [("new", raw.new_pyr[0][..., 0], 4), ("ref", raw.ref_pyr[0][..., 0], 4)] + tile_images()
+    for name, img, levels in cases:
+        pg, gg = dev(img, levels)
+        po, go = dir_pyramid(img, levels)
+        for l in range(levels):
+            # all three texel lanes and absSquaredGrad, bitwise (an inf intensity compares equal to itself)
+            assert pg[l].tobytes() == po[l].tobytes(), (name, l)
+            assert gg[l].tobytes() == go[l].tobytes(), (name, l)
 
 
 @pytest.mark.gpu

@@ -2,9 +2,8 @@
 python tools/image_time.py [--out FILE]
 
 Per size (640x480 with 4 levels, 1232x368 with 5), on one textured raw u8 frame, after 5 warm-up rounds and over 40
-rounds that alternate the two sides of each comparison:
-  build    device time of one frame's build: hs_image_set_u8's two kernels (hs_image_last_stats) against the launchers
-           they replace, hs_undist_enqueue + hs_build_dir_pyramid on one stream between two events (hs_image_time_chain)
+rounds that alternate the hand-off's two sides:
+  build    device time of one frame's build: hs_image_set_u8's two kernels (hs_image_last_stats)
   handoff  one keyframe's image hand-off, from the raw u8 frame in host memory to tracker frame, tracer frame, tracer
            host slot, selector map, extractor result and BA window image all set, each path ending in a synchronise of
            the device:
@@ -12,8 +11,9 @@ rounds that alternate the two sides of each comparison:
              parent  hs_tracker_set_frame_u8, hs_tracer_set_frame_u8, hs_undistorter_apply -> host fImgL ->
                      hs_selector_make_maps_raw, hs_dir_pyramid's level 0 on the host -> hs_tracer_set_host_image,
                      hs_extractor_extract_u8, hs_tracker_frame_to_ba: each leg as the library offered it before
-Times are p10 / median / p90 in microseconds; `*_spread_us` is the larger p90 - p10 of the two sides.  The tool also
-asserts that both paths leave the consumers bit-equal.  Not a test and no pass bar: a measurement."""
+Times are p10 / median / p90 in microseconds; `build_spread_us` is the build's p90 - p10, `handoff_spread_us` the
+larger p90 - p10 of the two sides.  The tool also asserts that both paths leave the consumers bit-equal.  Not a test
+and no pass bar: a measurement."""
 import ctypes as C
 import json
 import os
@@ -127,7 +127,7 @@ def measure(case):
         assert lib.hipDeviceSynchronize() == 0
         return n
 
-    t_new, t_par, d_new, d_old = [], [], [], []
+    t_new, t_par, d_new = [], [], []
     for i in range(WARMUP + ROUNDS):
         t0 = time.perf_counter()
         na = new_path(i)
@@ -135,22 +135,18 @@ def measure(case):
         nb = parent_path(i)
         t2 = time.perf_counter()
         assert na == nb, (na, nb)           # both selectors walk the same potential sequence
-        # the build alone, interleaved the same way (the hand-off's own set is the fused one)
-        fused_ms = im.last_stats()
-        chain_ms = im.time_chain(u, raw)
+        fused_ms = im.last_stats()          # the build alone: the hand-off's own set
         if i >= WARMUP:
             t_new.append(t1 - t0)
             t_par.append(t2 - t1)
             d_new.append(fused_ms)
-            d_old.append(chain_ms)
     a, b = new.observe(lib, levels), par.observe(lib, levels)
     assert len(a) == len(b) and all(x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a, b)), \
         "the two hand-offs left different consumers"
     q = lambda v, s: [round(float(np.percentile(v, p)) * s, 1) for p in (10, 50, 90)]  # noqa: E731
-    qn, qp, qf, qc = q(t_new, 1e6), q(t_par, 1e6), q(d_new, 1e3), q(d_old, 1e3)
+    qn, qp, qf = q(t_new, 1e6), q(t_par, 1e6), q(d_new, 1e3)
     out = {"size": f"{w}x{h}", "levels": levels, "rounds": ROUNDS,
-           "build_fused_us_p10_p50_p90": qf, "build_chain_us_p10_p50_p90": qc,
-           "build_spread_us": round(max(qf[2] - qf[0], qc[2] - qc[0]), 1),
+           "build_fused_us_p10_p50_p90": qf, "build_spread_us": round(qf[2] - qf[0], 1),
            "handoff_new_us_p10_p50_p90": qn, "handoff_parent_us_p10_p50_p90": qp,
            "handoff_spread_us": round(max(qn[2] - qn[0], qp[2] - qp[0]), 1), "same_consumers": True}
     for o in (new, par, im, u):
