@@ -1105,6 +1105,7 @@ void hs_destroy(hs_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->abort_thread.joinable()) c->abort_thread.join();  // an aborted communicator (comm_fail)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  map_forget(c);
   free_buffers(c);
   c->pool.release_all();
   if (c->comm) ncclCommDestroy(c->comm);

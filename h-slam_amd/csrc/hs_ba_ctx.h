@@ -17,6 +17,8 @@
 #include "hs_kernels.h"
 #include "hs_win_kernels.h"
 
+struct hs_map;  // hs_map_host.h
+
 #define HS_NCCL(x)                                                                                            \
   do {                                                                                                        \
     ncclResult_t r_ = (x);                                                                                    \
@@ -137,6 +139,7 @@ struct hs_ctx : hs::Device {
   std::vector<HsStagedPoint> staged;              // points inserted since the last commit
   std::vector<int> loc_key, loc_idx;              // handle -> (host frame key, index in its list); key -1 = gone
   int next_handle = 0, next_frame_key = 0;
+  hs_map* map = nullptr;                          // the attached point map (hs_ba_attach_map): removals append to it
   std::vector<int> pt_handle;                     // committed: handle of the point at each device position
   uint8_t* h_stage = nullptr;                     // pinned upload staging of a commit
   size_t h_stage_cap = 0;
@@ -318,4 +321,5 @@ int wait_stream(hs_ctx* c);
 int comm_fail(hs_ctx* c, const std::string& msg);  // abort the communicator, HS_ERR_RCCL
 // HsDevState::status of a finished launch chain -> the C-ABI code (HS_STATUS_STALE first: HS_ERR_STATE)
 int status_error(int status);
+void map_forget(hs_ctx* c);  // hs_map.cpp: the context and its attached map part
 }  // namespace hs

@@ -21,6 +21,7 @@
 
 #include "hs_ba_ctx.h"
 #include "hs_image_kernels.h"
+#include "hs_map_host.h"
 
 using namespace hs;
 
@@ -646,8 +647,34 @@ int hs_ba_remove_points(hs_ctx* c, int n, const int* handles) {
 int hs_ba_remove_points_without_residuals(hs_ctx* c, int* handles_out, int* n_out) {
   HS_TRY(ensure_incremental(c));
   std::vector<int> out;
+  std::vector<int> pos_of;  // with a map: handle -> committed position of the points that leave
+  if (c->map) {
+    // The records are copies of the device state at the points' committed positions, which pending edits leave where
+    // it is: only a leaving point that was never committed (inserted since the last commit) needs the commit first.
+    // The points are counted before any leaves (HS_ERR_NOMEM changes nothing).
+    int n = 0;
+    bool staged = false;
+    for (auto& l : c->wpts)
+      for (const WinPoint& w : l)
+        if (w.nres == 0) {
+          staged = staged || w.src < 0;
+          n++;
+        }
+    HS_TRY(map_room(c, n));
+    if (staged) HS_TRY(commit_if_dirty(c));
+    pos_of.assign(c->loc_key.size(), -1);
+    for (auto& l : c->wpts)
+      for (const WinPoint& w : l)
+        if (w.nres == 0) pos_of[w.handle] = w.src;
+  }
   for (int f = 0; f < (int)c->wframes.size(); f++)
     compact_list(c, f, [](const WinPoint& w) { return w.nres == 0; }, &out);
+  if (c->map && !out.empty()) {  // removal order is the reference's push order
+    std::vector<int> pos(out.size());
+    for (size_t i = 0; i < out.size(); i++) pos[i] = pos_of[out[i]];
+    const std::vector<uint8_t> st(out.size(), (uint8_t)HS_PT_OUTLIER);
+    HS_TRY(map_retire_listed(c, (int)out.size(), pos.data(), out.data(), st.data()));
+  }
   if (!out.empty()) c->dirty = true;
   if (handles_out && !out.empty()) std::memcpy(handles_out, out.data(), sizeof(int) * out.size());
   if (n_out) *n_out = (int)out.size();
@@ -873,6 +900,8 @@ int hs_ba_flag_points_for_removal(hs_ctx* c, int n_marg_frames, const int* marg_
   if (action_out && nP > 0) std::memcpy(action_out, h_action, nP);
   if (counts_out) std::memcpy(counts_out, h_counts, 6 * sizeof(int));
   if (apply) {
+    // an attached map takes the leaving points first, from the state the decision read (no room: nothing has changed)
+    if (c->map) HS_TRY(map_retire_flagged(c, h_action, h_counts[4] + h_counts[5]));
     // without a marginalized point HM / bM / hm_zero stay as they are (marginalizePointsF over an empty set)
     if (h_counts[5] > 0) HS_TRY(marginalize_flagged(c, true));
     // the removals in flagPointsForRemoval's order, while the pass runs (a committed point's src is its position)

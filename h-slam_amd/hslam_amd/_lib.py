@@ -62,6 +62,18 @@ class hs_undist_calib(C.Structure):  # include/hs_undist.h
                 ("desired_K", C.c_double * 4)]
 
 
+class hs_map_record(C.Structure):  # include/hs_map.h
+    _fields_ = [("handle", C.c_int32), ("frame_id", C.c_int32), ("status", C.c_int32), ("numGoodResiduals", C.c_int32),
+                ("u", C.c_float), ("v", C.c_float), ("idepth", C.c_float), ("idepth_zero", C.c_float),
+                ("hdif", C.c_float), ("maxRelBaseline", C.c_float), ("color", C.c_uint8 * 8),
+                ("reserved", C.c_uint8 * 16)]
+
+
+class hs_frame_marg_params(C.Structure):  # include/hs_map.h
+    _fields_ = [("minFrameAge", C.c_int), ("maxFrames", C.c_int), ("minFrames", C.c_int),
+                ("minPointsRemaining", C.c_float), ("maxLogAffFacInWindow", C.c_float)]
+
+
 # exported symbols of include/hs_ba.h (argument types)
 VP, I, D = C.c_void_p, C.c_int, C.c_double
 SIGNATURES = {
@@ -244,6 +256,21 @@ SIGNATURES = {
     "hs_refiner_set_points_flow": ([VP, VP, VP, VP], I),
     "hs_refiner_get_videpth": ([VP, VP], I),
     "hs_refiner_seed_ba": ([VP, VP, I, VP, VP, VP], I),
+    # include/hs_map.h
+    "hs_map_create": ([VP, I, I], I),
+    "hs_map_destroy": ([VP], None),
+    "hs_ba_attach_map": ([VP, VP], I),
+    "hs_map_retire_points": ([VP, I, VP, VP], I),
+    "hs_map_size": ([VP, VP, VP], I),
+    "hs_map_frame_counts": ([VP, I, VP, VP], I),
+    "hs_map_get_records": ([VP, I, I, VP], I),
+    "hs_map_clear": ([VP], I),
+    "hs_map_refresh_cloud": ([VP, VP, I, VP, VP, I, VP, VP], I),
+    "hs_map_cloud_device": ([VP, VP, VP, VP], I),
+    "hs_frame_marg_params_default": ([VP], I),
+    "hs_ba_flag_frames_for_marginalization": ([VP] * 6, I),
+    # test hook (not in the header): the frame rule of hs_ba_flag_frames_for_marginalization on the host
+    "hs_debug_frame_rule": ([I] + [VP] * 8, I),
 }
 
 _lib = None

@@ -276,6 +276,35 @@ class BAWindow:
             o.update(HM=HM, bM=bM)
         return o
 
+    def attachMap(self, point_map):
+        """hs_ba_attach_map: the window's removals (flagPointsForRemoval(apply), removeOutliers) append a record per
+        point to `point_map` (hslam_amd.map.PointMap) before the point leaves; None detaches."""
+        check(self.lib.hs_ba_attach_map(self.h, None if point_map is None else point_map.h))
+        self.map = point_map
+
+    def retirePoints(self, handles, status):
+        """hs_map_retire_points: records of the points `handles` (status 1 OUTLIER / 3 MARGINALIZED each) for a caller
+        that decides itself; call it before removePoints."""
+        hd = np.ascontiguousarray(handles, np.int32)
+        st = np.ascontiguousarray(status, np.uint8)
+        check(self.lib.hs_map_retire_points(self.h, len(hd), ptr(hd), ptr(st)))
+
+    def flagFramesForMarginalization(self, kf_id, n_immature=None, params=None):
+        """System::flagFramesForMarginalization on the committed window (needs an attached map): kf_id [nF] the
+        frames' KfId, n_immature [nF] their immature-point counts (None: 0), params an hs_frame_marg_params (None: the
+        reference's settings).  Returns the flags [nF] (uint8)."""
+        self._sync()
+        kf = np.ascontiguousarray(kf_id, np.int32)
+        ni = None if n_immature is None else np.ascontiguousarray(n_immature, np.int32)
+        if len(kf) != self.nF or (ni is not None and len(ni) != self.nF):
+            raise ValueError("kf_id / n_immature must have one entry per window frame")
+        out = np.zeros(self.nF, np.uint8)
+        n = C.c_int()
+        check(self.lib.hs_ba_flag_frames_for_marginalization(self.h, None if params is None else C.addressof(params),
+                                                             ptr(kf), ptr(ni), ptr(out), C.byref(n)))
+        assert n.value == int((out != 0).sum())
+        return out
+
     def synchronize(self):
         check(self.lib.hs_ba_synchronize(self.h))
 

@@ -18,7 +18,10 @@ bookkeeping) are the caller's code in the reference too; they run here in numpy 
 work.  KeyframeBA(decisions="device") hands flagPointsForRemoval to the library instead: one
 hs_ba_flag_points_for_removal call decides on the device (the context keeps lastResiduals itself), runs
 marginalizePointsF and removes the points; that call is timed with the library work.  Frame policy: the window holds ``window`` keyframes during optimize and the oldest is marginalized afterwards
-(flagFramesForMarginalization's steady state; its distance score and point-count rules are not modelled).
+(flagFramesForMarginalization's steady state).  KeyframeBA(map=PointMap(...)) attaches a point map (include/hs_map.h): every
+point that leaves the window leaves a record there.  KeyframeBA(frame_policy="reference") takes the frames to
+marginalize from hs_ba_flag_frames_for_marginalization instead (the reference's point-count, affine and distance-score
+rules, with the map's counters; maxFrames = ``window``); it needs a map and decisions="device".
 """
 from __future__ import annotations
 
@@ -149,9 +152,13 @@ class KeyframeBA:
 
     def __init__(self, seq: BASequence, device: int = 0, window: int = 8, capacity: int = 0, params=None,
                  tracker=None, image_path: str = "raw", iters: int = 6, allow_break: bool = False,
-                 decisions: str = "host"):
+                 decisions: str = "host", map=None, frame_policy: str = "oldest"):
         if decisions not in ("host", "device"):
             raise ValueError("decisions must be 'host' or 'device'")
+        if frame_policy not in ("oldest", "reference"):
+            raise ValueError("frame_policy must be 'oldest' or 'reference'")
+        if frame_policy == "reference" and (map is None or decisions != "device"):
+            raise ValueError("frame_policy='reference' needs a map and decisions='device'")
         # flagPointsForRemoval: "host" decides here in numpy from read-backs (the module docstring's caller code);
         # "device" is one hs_ba_flag_points_for_removal call (the library keeps lastResiduals itself)
         self.decisions = decisions
@@ -167,6 +174,16 @@ class KeyframeBA:
         cap = capacity or ppk * (window + 2) + 64
         self.ba = BAWindow(camera=(seq.width, seq.height, seq.n_levels, seq.K), capacity=cap, device=device,
                            params=params)
+        # the point map the window's removals append to (None: none, today's path), and who picks the frame to
+        # marginalize: "oldest" (frame 0 once the window is full) or "reference" (flagFramesForMarginalization)
+        self.map = map
+        self.frame_policy = frame_policy
+        self.frame_params = None
+        if map is not None:
+            self.ba.attachMap(map)
+        if frame_policy == "reference":  # the reference's settings with the driver's window size
+            from .map import frame_marg_params
+            self.frame_params = frame_marg_params(maxFrames=window, minFrames=min(5, window - 1))
         self.frames = []                 # window frames as sequence indices (frameHessians order)
         self.cand_of = {}                # handle -> (host sequence index, candidate index)
         self.last_state = {}             # handle -> [lastResiduals[0].second, [1].second] (System bookkeeping)
@@ -270,7 +287,36 @@ class KeyframeBA:
             timer.run("post", self.tracker.set_ref_ba, ba, self.image_path in ("device", "device_ptr"))
         # flagPointsForRemoval (Src/Mapping.cpp:248-328), the frame to marginalize: the oldest once the window is full
         info = dict(energies=energies, iters=n_it, n_points=ba.n_points, n_res=ba.n_res, dropped_points=len(gone))
-        if marginalize and len(self.frames) >= self.window and not host_rule:
+        if marginalize and self.frame_policy == "reference":
+            # flagFramesForMarginalization decides (KfId = the sequence index; the newest keyframe's candidates are its
+            # immature points), then flagPointsForRemoval and marginalizeFrame of every flagged frame
+            kf_id = np.asarray(self.frames, np.int32)
+            n_imm = np.zeros(len(self.frames), np.int32)
+            n_imm[-1] = len(self.seq.cand[self.frames[-1]]["u"])
+            self.frame_inputs = dict(kf_id=kf_id, n_immature=n_imm)
+            if check:
+                check(self, "flag_frames")
+            fl = self.frame_flags = timer.run("post", ba.flagFramesForMarginalization, kf_id, n_imm, self.frame_params)
+            marg_fs = [int(f) for f in np.nonzero(fl)[0]]
+            hd_all = ba.structure()["handles"]
+            self.marg_points, self.marg_frame, self.marg_frames = None, (marg_fs[0] if marg_fs else None), marg_fs
+            if check:
+                check(self, "marginalize")
+            flg = self.last_flags = timer.run("post", ba.flagPointsForRemoval, marg_fs, True, False)
+            marg, drop = flg["action"] == 2, flg["action"] == 1
+            self.marg_points = np.nonzero(marg)[0].astype(np.int32)
+            self.marg_handles, self.drop_handles = hd_all[marg], hd_all[drop]
+            if check:
+                check(self, "points_marginalized")
+            for hd in hd_all[marg | drop]:
+                self.cand_of.pop(int(hd), None)
+            for f in reversed(marg_fs):
+                timer.run("post", ba.removeFrame, f, True)
+                self.frames.pop(f)
+            if check:
+                check(self, "frame_marginalized")
+            info.update(marginalized_points=int(marg.sum()), dropped=int(drop.sum()), marg_frames=marg_fs)
+        elif marginalize and len(self.frames) >= self.window and not host_rule:
             # the decisions, marginalizePointsF and the removals in one library call; only the actions come back
             marg_f = 0
             hd_all = ba.structure()["handles"]
