@@ -5,6 +5,10 @@
 //                     PRE_tTll / PRE_aff_mode (FrameFramePrecalc::set) from the frames of the BA's device state: one
 //                     thread per (host, target) pair, the diagonal threads also their frame.  The arithmetic is
 //                     hs_host_math.h's make_act_*, the same inlines hs_debug_act_inputs runs on the host.
+//   hs_k_trc_form     traceNewCoarse's per-host KRKi / Kt / aff (Src/Mapping.cpp:500-513) of hs_tracer_trace_ba: one
+//                     thread per window frame at its committed index, against the new frame's pose / affine pair /
+//                     exposure (by value), into the tracer's host table at the frame's slot.  hs_host_math.h's
+//                     make_trace_host, the inline hs_debug_trace_hosts runs on the host.
 //   hs_k_act_stage    the activated points as HsStagedPoint records in toOptimize order (the hs_k_win_gather's second
 //                     staged source).  One workgroup: ballot prefix sums per chunk of the list give every activated
 //                     entry its rank (no atomics: the order is the list's), then one lane per (point, pattern slot)
@@ -34,6 +38,14 @@ __global__ __launch_bounds__(64) void hs_k_act_form(HsActFormArgs a) {
     hs::make_act_K(a.st->calib, K1, Ki0);
     hs::make_act_frame(a.st->frames[h], a.st->frames[nF - 1], K1, Ki0, f.KRKi, f.Kt);
   }
+}
+
+__global__ __launch_bounds__(64) void hs_k_trc_form(HsTrcFormArgs a) {
+  const int f = threadIdx.x;
+  if (f >= a.nF) return;
+  const hs::SE3 nw = hs::SE3::fromData(a.new_worldToCam);
+  hs::make_trace_host(a.st->frames[a.idx[f]], nw, a.new_exposure, a.new_aff[0], a.new_aff[1], a.st->calib,
+                      &a.hosts[a.slot[f]]);
 }
 
 using hs_imm::block_rank;

@@ -13,6 +13,7 @@
 #include <limits>
 #include <vector>
 
+#include "../../include/hs_trace.h"
 #include "../../include/hs_types.h"
 #include "hs_layout.h"
 #include "hs_se3.h"
@@ -237,6 +238,31 @@ HS_HD inline void make_act_pair(const FrameH& H, const FrameH& T, float RTll[9],
   fromToVecExposure(H.ab_exposure, T.ab_exposure, H.aff_a(), H.aff_b(), T.aff_a(), T.aff_b(), a);
   aff[0] = (float)a[0];
   aff[1] = (float)a[1];
+}
+
+// ---- traceNewCoarse's per-host traceOn arguments (hs_trace_host, include/hs_trace.h; Src/Mapping.cpp:500-513), written
+// once for the device (hs_k_trc_form, hs_act_ba_kernels.hip) and the host (hs_debug_trace_hosts), with make_act_*'s
+// rounding rules.  K is the level-0 value_scaledf matrix (activation's K[1] is another one); the new frame is not a
+// window frame yet, so its pose, affine pair and exposure come by value.
+HS_HD inline void make_trace_host(const FrameH& host, const SE3& newWorldToCam, float newExposure, double newA,
+                                  double newB, const CalibH& cal, hs_trace_host* out) {
+#pragma clang fp contract(off)
+  const SE3 hostToNew = newWorldToCam * host.PRE_camToWorld;
+  double R[9];
+  hostToNew.rotationMatrix(R);
+  float Rf[9], tf[3], KR[9], Ki[9];
+  for (int i = 0; i < 9; i++) Rf[i] = (float)R[i];
+  for (int i = 0; i < 3; i++) tf[i] = (float)hostToNew.t[i];
+  const float K[9] = {cal.value_scaledf[0], 0, cal.value_scaledf[2], 0, cal.value_scaledf[1], cal.value_scaledf[3],
+                      0, 0, 1};
+  inv3f(K, Ki);
+  mm3f(K, Rf, KR);
+  mm3f(KR, Ki, out->KRKi);
+  mv3f(K, tf, out->Kt);
+  double a[2];
+  fromToVecExposure(host.ab_exposure, newExposure, host.aff_a(), host.aff_b(), newA, newB, a);
+  out->aff[0] = (float)a[0];
+  out->aff[1] = (float)a[1];
 }
 
 // setAdjointsF for one (h, t): AH, AT (row-major 8x8, fp64) + float copies

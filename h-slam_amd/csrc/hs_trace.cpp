@@ -78,6 +78,9 @@ struct hs_tracer : hs::Device {
   unsigned in_seq = 0;
   int in_nF = 0, in_n_active = 0;
   float in_K4[4] = {0, 0, 0, 0};
+  // what the last hs_tracer_trace_ba formed (hs_tracer_get_trace_inputs): the slots it wrote in d_hosts
+  int trc_n_hosts = 0;
+  bool trc_named[HS_TRC_MAXHOST] = {false};
 };
 
 static HsCmpPointSet live_set(hs_tracer* t) {
@@ -351,16 +354,9 @@ int hs_tracer_set_host_image_from(hs_tracer* t, int slot, hs_image* im) {
   return copy_image_level0(t, t->d_host_img[slot], im, v);
 }
 
-int hs_tracer_trace(hs_tracer* t, int n_hosts, const hs_trace_host* hosts, int counts6[6]) {
-  if (!t || (n_hosts > 0 && !hosts)) return hs::fail(HS_ERR_INVALID, "null argument");
-  if (n_hosts < 0 || n_hosts > HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "n_hosts out of range");
-  if (!t->have_frame) return hs::fail(HS_ERR_STATE, "no frame to trace on (hs_tracer_set_frame)");
-  HS_HIP(hipSetDevice(t->device));
-  if (t->n > 0) {
-    // every point's host slot must have its (KRKi, Kt, aff)
-    if (t->max_host >= n_hosts) return hs::fail(HS_ERR_INVALID, "a point's host slot has no hs_trace_host entry");
-    HS_HIP(hipMemcpyAsync(t->d_hosts, hosts, sizeof(hs_trace_host) * n_hosts, hipMemcpyHostToDevice, t->stream));
-  }
+// traceOn of every point against t->d_new with the (KRKi, Kt, aff) records in t->d_hosts, then the tallies: the one
+// launch hs_tracer_trace and hs_tracer_trace_ba share
+static int trace_launch(hs_tracer* t, int counts6[6]) {
   HsTraceArgs a;
   a.n = t->n;
   a.W = t->W;
@@ -405,6 +401,19 @@ int hs_tracer_trace(hs_tracer* t, int n_hosts, const hs_trace_host* hosts, int c
   HS_TRY(sync_stats(t));
   for (int k = 0; k < 6; k++) counts6[k] = t->h_counts[k];
   return HS_OK;
+}
+
+int hs_tracer_trace(hs_tracer* t, int n_hosts, const hs_trace_host* hosts, int counts6[6]) {
+  if (!t || (n_hosts > 0 && !hosts)) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (n_hosts < 0 || n_hosts > HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "n_hosts out of range");
+  if (!t->have_frame) return hs::fail(HS_ERR_STATE, "no frame to trace on (hs_tracer_set_frame)");
+  HS_HIP(hipSetDevice(t->device));
+  if (t->n > 0) {
+    // every point's host slot must have its (KRKi, Kt, aff)
+    if (t->max_host >= n_hosts) return hs::fail(HS_ERR_INVALID, "a point's host slot has no hs_trace_host entry");
+    HS_HIP(hipMemcpyAsync(t->d_hosts, hosts, sizeof(hs_trace_host) * n_hosts, hipMemcpyHostToDevice, t->stream));
+  }
+  return trace_launch(t, counts6);
 }
 
 int hs_tracer_get_points(hs_tracer* t, int* n, uint8_t* status, float* idepth_min, float* idepth_max, float* quality,
@@ -1066,6 +1075,110 @@ int hs_tracer_get_act_inputs(hs_tracer* t, hs_ctx* ba, float K4[4], int* nF, hs_
     if (n && act_u) HS_HIP(hipMemcpy(act_u, ba->d_u, 4 * n, hipMemcpyDeviceToHost));
     if (n && act_v) HS_HIP(hipMemcpy(act_v, ba->d_v, 4 * n, hipMemcpyDeviceToHost));
     if (n && act_idepth) HS_HIP(hipMemcpy(act_idepth, ba->d_idepth, 4 * n, hipMemcpyDeviceToHost));
+  }
+  return HS_OK;
+}
+
+// ---- traceNewCoarse whose window is a BA context's ---------------------------------------------------------------
+
+int hs_tracer_trace_ba(hs_tracer* t, hs_ctx* ba, int nF, const int* slots, const double new_worldToCam[7],
+                       const double new_aff_g2l[2], float new_ab_exposure, int counts6[6]) {
+  if (!t || !ba || !slots || !new_worldToCam || !new_aff_g2l) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (ba->comm_lost) return hs::fail(HS_ERR_RCCL, "communicator aborted by an earlier call (a peer rank failed)");
+  if (ba->multi_rank()) return hs::fail(HS_ERR_STATE, "hs_tracer_trace_ba needs a single-rank BA context");
+  if (ba->device != t->device) return hs::fail(HS_ERR_INVALID, "tracer and BA context on different devices");
+  if (!ba->d_state || !ba->haveCam) return hs::fail(HS_ERR_STATE, "the BA context has no window");
+  if (ba->cam.width != t->W || ba->cam.height != t->H) return hs::fail(HS_ERR_INVALID, "image size mismatch");
+  const int wnF = ba->incremental ? (int)ba->wframes.size() : ba->nF;
+  if (nF < 1 || nF > HS_MAXF || nF != wnF)
+    return hs::fail(HS_ERR_INVALID, "nF differs from the BA window's number of frames");
+  if (!t->have_frame) return hs::fail(HS_ERR_STATE, "no frame to trace on (hs_tracer_set_frame)");
+  bool named[HS_TRC_MAXHOST] = {false};
+  int n_hosts = 0;
+  for (int f = 0; f < nF; f++) {
+    const int sl = slots[f];
+    if (sl < 0 || sl >= HS_TRC_MAXHOST) return hs::fail(HS_ERR_INVALID, "window frame's slot out of range");
+    if (named[sl]) return hs::fail(HS_ERR_INVALID, "two window frames on one slot");
+    named[sl] = true;
+    n_hosts = std::max(n_hosts, sl + 1);
+  }
+  // every point's host slot must be a window frame's (the host mirror of the points' slots: no read-back)
+  for (int i = 0; i < t->n; i++)
+    if (!named[t->h_host[i]]) return hs::fail(HS_ERR_INVALID, "an immature point on a slot that is no window frame's");
+  HS_HIP(hipSetDevice(t->device));
+  // The frames are read at their committed index, which pending removals and point edits leave as it is (the steady
+  // state: the last keyframe's hs_ba_remove_frame is still uncommitted), so those commit nothing here; a frame
+  // inserted since the last commit is on the device only after it.
+  bool inserted = false;
+  if (ba->incremental)
+    for (int f = 0; f < nF; f++) inserted = inserted || ba->wframes[f].committed < 0;
+  if (inserted) HS_TRY(hs_ba_make_idx(ba, nullptr, nullptr, nullptr));
+  HsTrcFormArgs fa;
+  fa.nF = nF;
+  for (int f = 0; f < 8; f++) {
+    fa.idx[f] = f < nF ? (ba->incremental ? ba->wframes[f].committed : f) : 0;
+    fa.slot[f] = f < nF ? slots[f] : 0;
+    if (fa.idx[f] < 0 || fa.idx[f] >= HS_MAXF) return hs::fail(HS_ERR_STATE, "a window frame has no committed index");
+  }
+  memcpy(fa.new_worldToCam, new_worldToCam, sizeof(fa.new_worldToCam));
+  fa.new_aff[0] = new_aff_g2l[0];
+  fa.new_aff[1] = new_aff_g2l[1];
+  fa.new_exposure = new_ab_exposure;
+  fa.st = ba->d_state;
+  fa.hosts = t->d_hosts;
+  hipStream_t s = t->stream;
+  // the tracer's stream after the BA's: the frames' state as the last GN step / commit left it
+  HS_HIP(hipEventRecord(ba->ev_ready, ba->stream));
+  HS_HIP(hipStreamWaitEvent(s, ba->ev_ready, 0));
+  hipLaunchKernelGGL(hs_k_trc_form, dim3(1), dim3(64), 0, s, fa);
+  HS_HIP(hipGetLastError());
+  t->trc_n_hosts = n_hosts;
+  memcpy(t->trc_named, named, sizeof(named));
+  return trace_launch(t, counts6);
+}
+
+int hs_tracer_get_trace_inputs(hs_tracer* t, int* n_hosts, hs_trace_host* hosts) {
+  if (!t) return hs::fail(HS_ERR_INVALID, "null tracer");
+  if (!t->trc_n_hosts) return hs::fail(HS_ERR_STATE, "no hs_tracer_trace_ba has run");
+  if (n_hosts) *n_hosts = t->trc_n_hosts;
+  if (!hosts) return HS_OK;
+  HS_HIP(hipSetDevice(t->device));
+  HS_HIP(hipStreamSynchronize(t->stream));
+  HS_HIP(hipMemcpy(hosts, t->d_hosts, sizeof(hs_trace_host) * t->trc_n_hosts, hipMemcpyDeviceToHost));
+  for (int sl = 0; sl < t->trc_n_hosts; sl++)  // slots of no window frame: nothing was formed there
+    if (!t->trc_named[sl]) memset(&hosts[sl], 0, sizeof(hs_trace_host));
+  return HS_OK;
+}
+
+// test hook (not in the header, no device work): hs_host_math.h's make_trace_host on the host -- the inline
+// hs_k_trc_form runs.  The host frames come from a device-state blob (hs_debug_get_state) at the indices idx [nF]
+// (NULL: 0 .. nF-1), or, with state == NULL, from nF poses as hs_debug_act_inputs takes them; the new frame from its
+// worldToCam [7], aff_g2l (a, b) and exposure.  Out: hosts [nF], in frame order.
+int hs_debug_trace_hosts(const void* state, int nF, const int* idx, const double* worldToCam, const double* aff,
+                         const float* exposure, const float* K4, const double* new_worldToCam, const double* new_aff,
+                         float new_exposure, hs_trace_host* hosts) {
+  if (nF < 1 || nF > HS_MAXF || !new_worldToCam || !new_aff || !hosts) return hs::fail(HS_ERR_INVALID, "bad argument");
+  const hs::SE3 nw = hs::SE3::fromData(new_worldToCam);
+  if (state) {
+    const HsDevState* S = static_cast<const HsDevState*>(state);
+    for (int f = 0; f < nF; f++) {
+      const int k = idx ? idx[f] : f;
+      if (k < 0 || k >= HS_MAXF) return hs::fail(HS_ERR_INVALID, "frame index out of range");
+      hs::make_trace_host(S->frames[k], nw, new_exposure, new_aff[0], new_aff[1], S->calib, &hosts[f]);
+    }
+    return HS_OK;
+  }
+  if (!worldToCam || !aff || !exposure || !K4) return hs::fail(HS_ERR_INVALID, "bad argument");
+  hs::CalibH cal;
+  for (int k = 0; k < 4; k++) cal.value_scaledf[k] = K4[k];
+  for (int f = 0; f < nF; f++) {
+    hs::FrameH fr;
+    fr.PRE_worldToCam = hs::SE3::fromData(worldToCam + 7 * f);
+    fr.PRE_camToWorld = fr.PRE_worldToCam.inverse();
+    fr.state_scaled[6] = aff[2 * f];
+    fr.state_scaled[7] = aff[2 * f + 1];
+    fr.ab_exposure = exposure[f];
+    hs::make_trace_host(fr, nw, new_exposure, new_aff[0], new_aff[1], cal, &hosts[f]);
   }
   return HS_OK;
 }

@@ -161,6 +161,18 @@ struct HsActFormArgs {
   hs_act_pair* pairs;        // [nF*nF] host*nF + target
 };
 
+// traceNewCoarse's hs_trace_host records of the window's frames against a new frame (hs_host_math.h make_trace_host):
+// window frame f lies at st->frames[idx[f]] (its committed index) and writes hosts[slot[f]]
+struct HsTrcFormArgs {
+  int nF;
+  int idx[8], slot[8];
+  double new_worldToCam[7];  // the new frame: SE3 data, aff_g2l (a, b), ab_exposure
+  double new_aff[2];
+  float new_exposure;
+  const HsDevState* st;
+  hs_trace_host* hosts;      // [HS_TRC_MAXHOST]
+};
+
 // one HsStagedPoint per activated point, in toOptimize order, into the BA context's staging array
 struct HsActStageArgs {
   int n;                     // toOptimize entries
@@ -197,6 +209,7 @@ struct HsCmpArgs {
 };
 
 __global__ void hs_k_act_form(HsActFormArgs a);
+__global__ void hs_k_trc_form(HsTrcFormArgs a);
 __global__ void hs_k_act_stage(HsActStageArgs a);
 __global__ void hs_k_cmp_flags(HsCmpArgs a);
 __global__ void hs_k_cmp_scan(HsCmpArgs a, int nblk);

@@ -177,6 +177,10 @@ SIGNATURES = {
     "hs_debug_act_inputs": ([VP, I, VP, VP, VP, VP, VP, VP, VP], I),
     "hs_debug_act_mirror": ([I, I, VP, VP, VP, VP], I),
     "hs_debug_commit_count": ([VP], I),
+    "hs_tracer_trace_ba": ([VP, VP, I, VP, VP, VP, C.c_float, VP], I),
+    "hs_tracer_get_trace_inputs": ([VP, VP, VP], I),
+    # test hook (not in the header, no device work): the formed trace inputs on the host
+    "hs_debug_trace_hosts": ([VP, I, VP, VP, VP, VP, VP, VP, VP, C.c_float, VP], I),
     "hs_tracer_set_frame": ([VP, VP], I),
     "hs_tracer_set_frame_raw": ([VP, VP], I),
     "hs_tracer_trace": ([VP, I, VP, VP], I),

@@ -22,6 +22,22 @@ marginalizePointsF and removes the points; that call is timed with the library w
 point that leaves the window leaves a record there.  KeyframeBA(frame_policy="reference") takes the frames to
 marginalize from hs_ba_flag_frames_for_marginalization instead (the reference's point-count, affine and distance-score
 rules, with the map's counters; maxFrames = ``window``); it needs a map and decisions="device".
+
+KeyframeBA(points="traced") replaces the invented points by traced ones, the whole chain on the device in the
+reference's order (needs decisions="device" and the "oldest" frame policy): the camera frame as one DeviceImage, shared
+by every consumer; traceNewCoarse against the window (ImmatureTracer.trace_ba: the hosts' KRKi / Kt / aff formed from the
+window's frames on the device); insertFrame with the image handed over on the device; activatePointsMT into the window
+(ImmatureTracer.activate_into, the driver keeps currentMinActDist); after flagPointsForRemoval, makeNewTraces on the
+new keyframe (PixelSelector.makeMapsImage, FeatureExtractor, ImmatureTracer.add_keys); marginalizeFrame.  trace_frame(k)
+is ProcessNonKeyframe: the frame and trace_ba.  A frame's tracer slot is its sequence index modulo 64.  The first
+window (bootstrap) still takes candidate points, so that it is well conditioned, and traces keys beside them.
+handoff="host" is the same chain with hs_tracer_trace fed ready hs_trace_host arrays (``trace_feed``: what a
+handoff="device" run recorded from trace_inputs() with record_inputs=True), the twin of tests and timing.
+Two things differ from a literal reading of the reference's steps.  A marginalized frame's immature points leave the
+tracer at once (ImmatureTracer.compact_device with the frame's slot in drop_slot), not with the next activation's
+compaction: trace_ba refuses points on a slot that is no window frame's, and non-keyframes are traced in between.  The
+extractor reads cvImgL as an 8-bit host image (extract_selected on the selector's device map), since a DeviceImage set
+from a float frame holds none.
 """
 from __future__ import annotations
 
@@ -52,6 +68,7 @@ class BASequence:
     raw: list                # [N] (h, w) float32 level-0 images (ImageData::fImgL)
     pyr0: list               # [N] (h, w, 3) float32 DirPyr[0]
     cand: list               # [N] dict(u, v, idepth, idepth_true, color [n, 8], weights [n, 8]): points hosted there
+    planes: list = None      # the scene (render_depth_at's truth for points the sequence did not plant)
 
     @property
     def n_frames(self):
@@ -106,7 +123,7 @@ def make_ba_sequence(n_kf: int = 12, points_per_kf: int = 250, width: int = 640,
                           idepth_true=it, color=np.ascontiguousarray(smp[..., 0], np.float32),
                           weights=np.ascontiguousarray(wgt)))
     return BASequence(width=width, height=height, K=K, n_levels=levels, poses=np.array(poses), evals=np.array(evals),
-                      raw=raws, pyr0=pyrs, cand=cands)
+                      raw=raws, pyr0=pyrs, cand=cands, planes=planes)
 
 
 def in_bounds_targets(seq: BASequence, host: int, targets, u, v, idepth):
@@ -152,9 +169,19 @@ class KeyframeBA:
 
     def __init__(self, seq: BASequence, device: int = 0, window: int = 8, capacity: int = 0, params=None,
                  tracker=None, image_path: str = "raw", iters: int = 6, allow_break: bool = False,
-                 decisions: str = "host", map=None, frame_policy: str = "oldest"):
+                 decisions: str = "host", map=None, frame_policy: str = "oldest", points: str = "candidates",
+                 handoff: str = "device", key_density: float = 600.0, max_keys: int = 2000, trace_feed=None,
+                 record_inputs: bool = False, trace_counts: bool = True):
         if decisions not in ("host", "device"):
             raise ValueError("decisions must be 'host' or 'device'")
+        if points not in ("candidates", "traced"):
+            raise ValueError("points must be 'candidates' or 'traced'")
+        if handoff not in ("device", "host"):
+            raise ValueError("handoff must be 'device' or 'host'")
+        if points == "traced" and (decisions != "device" or frame_policy != "oldest"):
+            raise ValueError("points='traced' needs decisions='device' and frame_policy='oldest'")
+        if points == "traced" and handoff == "host" and trace_feed is None:
+            raise ValueError("handoff='host' needs trace_feed (a handoff='device' run's recorded trace_inputs)")
         if frame_policy not in ("oldest", "reference"):
             raise ValueError("frame_policy must be 'oldest' or 'reference'")
         if frame_policy == "reference" and (map is None or decisions != "device"):
@@ -171,7 +198,7 @@ class KeyframeBA:
         self.tracker = tracker
         self.image_path = image_path
         ppk = len(seq.cand[0]["u"])
-        cap = capacity or ppk * (window + 2) + 64
+        cap = capacity or ppk * (window + 2) + 64 + (max_keys * window if points == "traced" else 0)
         self.ba = BAWindow(camera=(seq.width, seq.height, seq.n_levels, seq.K), capacity=cap, device=device,
                            params=params)
         # the point map the window's removals append to (None: none, today's path), and who picks the frame to
@@ -188,6 +215,90 @@ class KeyframeBA:
         self.cand_of = {}                # handle -> (host sequence index, candidate index)
         self.last_state = {}             # handle -> [lastResiduals[0].second, [1].second] (System bookkeeping)
         self.history = []
+        # the traced chain (module docstring): one device frame and its consumers
+        self.points = points
+        self.handoff = handoff
+        self.traced = points == "traced"
+        if self.traced:
+            from .extract import FeatureExtractor
+            from .image import DeviceImage
+            from .select import PixelSelector
+            from .trace import ImmatureTracer
+            self.key_density = key_density
+            self.trace_feed = trace_feed          # handoff="host": hs_trace_host arrays, one per trace, in call order
+            self.feed_pos = 0
+            self.record_inputs = record_inputs    # handoff="device": keep trace_inputs() of every trace in trace_log
+            self.trace_log = []
+            self.trace_counts = trace_counts
+            self.currentMinActDist = 2.0          # System::currentMinActDist's initial value
+            self.img = DeviceImage(seq.width, seq.height, seq.n_levels, device)
+            self.selector = PixelSelector(seq.width, seq.height, params, device)
+            # a descriptor sampling pattern (any will do: the chain reads the keys' positions only)
+            pattern = np.random.default_rng(7).integers(-13, 14, size=(256, 2, 2), dtype=np.int8)
+            self.extractor = FeatureExtractor(seq.width, seq.height, max_keys, pattern, device)
+            self.tracer = ImmatureTracer(seq.width, seq.height, max_keys * (window + 2), device, params)
+            self.trace_history = []
+
+    def close(self):
+        """Release the window and, in traced mode, the frame and its consumers."""
+        if self.traced:
+            self.tracer.close()
+            self.extractor.close()
+            self.selector.__del__()
+            self.img.close()
+        self.ba.close()
+
+    # ---------------------------------------------------------------- the traced chain
+    @staticmethod
+    def slot_of(k):
+        return int(k) % 64
+
+    def _set_frame(self, k, timer):
+        """The camera frame on the device, and the tracer's frame to trace on."""
+        timer.run("frame", self.img.set_raw, self.seq.raw[k])
+        timer.run("frame", self.tracer.set_frame_image, self.img)
+
+    def _trace(self, k, timer):
+        """traceNewCoarse(k) against the window as it stands; returns the status counts (None without trace_counts)."""
+        slots = [self.slot_of(f) for f in self.frames]
+        if self.handoff == "device":
+            c = timer.run("trace", self.tracer.trace_ba, self.ba, slots, self.seq.evals[k], (0.0, 0.0), 1.0,
+                          self.trace_counts)
+            if self.record_inputs:
+                self.trace_log.append(self.tracer.trace_inputs())
+        else:
+            hosts = self.trace_feed[self.feed_pos]
+            self.feed_pos += 1
+            c = timer.run("trace", self.tracer.trace_hosts, hosts, self.trace_counts)
+        self.trace_history.append(dict(frame=k, n_hosts=len(slots), n_points=self.tracer.n,
+                                       counts=None if c is None else c.copy()))
+        return c
+
+    def _make_new_traces(self, k, timer, set_image=True):
+        """System::makeNewTraces(k): the selector's map and the extractor's keys of the frame in self.img, one
+        immature point per key on the frame's slot (set_image: the slot's DirPyr[0] is not there yet)."""
+        slot = self.slot_of(k)
+        img8 = np.clip(np.rint(self.seq.raw[k]), 0, 255).astype(np.uint8)
+        timer.run("new_traces", self.selector.makeMapsImage, self.img, k, self.key_density, 1, 1.0, False)
+        timer.run("new_traces", self.extractor.extract_selected, self.selector, img8)
+        if set_image:
+            timer.run("new_traces", self.tracer.set_host_image_from, slot, self.img)
+        return timer.run("new_traces", self.tracer.add_keys, self.extractor, slot)
+
+    def _drop_frame_points(self, k, timer):
+        """marginalizeFrame(k)'s immature points: the frame's slot through drop_slot, compacted on the device."""
+        drop = np.zeros(64, np.uint8)
+        drop[self.slot_of(k)] = 1
+        before = self.tracer.n
+        timer.run("post", self.tracer.compact_device, np.ones(before, np.uint8), drop)
+        return before - self.tracer.n
+
+    def trace_frame(self, k):
+        """ProcessNonKeyframe(k): the frame and traceNewCoarse, nothing else.  Returns dict(counts, lib_s)."""
+        timer = _Timer()
+        self._set_frame(k, timer)
+        c = self._trace(k, timer)
+        return dict(counts=c, phase_s=dict(timer.t), lib_s=sum(timer.t.values()))
 
     # ---------------------------------------------------------------- helpers
     def _frame(self, k):
@@ -234,7 +345,9 @@ class KeyframeBA:
     # ---------------------------------------------------------------- the sequence
     def bootstrap(self, n_frames=None):
         """The first window: keyframes 0 .. n-1 with the points of frames 0 .. n-2 (the newest KF's points activate
-        with the next keyframe, as in the steady state)."""
+        with the next keyframe, as in the steady state).  In traced mode the window is built the same way, from
+        candidate points, and every bootstrap frame also gets its keys as immature points, traced on the later
+        bootstrap frames."""
         n = n_frames or self.window - 1
         timer = _Timer()
         for k in range(n):
@@ -242,6 +355,14 @@ class KeyframeBA:
         for k in range(n - 1):
             self._activate(k, timer)
         self.ba.makeIDX()
+        if self.traced:
+            # every bootstrap keyframe traced on the later ones as they come, then makeNewTraces on it: at frame k the
+            # tracer holds the points of frames < k (the window's later frames get records no point reads)
+            for k in range(n):
+                self._set_frame(k, timer)
+                if k > 0:
+                    self._trace(k, timer)
+                self._make_new_traces(k, timer)
 
     def add_keyframe(self, k, marginalize=True, check=None):
         """AddKeyframe(k)'s BA part.  check(driver, phase) is called at 'optimize' (before it), 'tail' (after the
@@ -251,12 +372,36 @@ class KeyframeBA:
         ba, timer = self.ba, _Timer()
         host_rule = self.decisions == "host"
         wall0 = time.perf_counter()
-        # insertFrame, new residuals of the old points, activation of the previous newest KF's points
-        self._insert_frame(k, timer)
-        timer.run("setup", ba.addResidualsToNewest)
-        for hd, st in self.last_state.items():
-            st[1], st[0] = st[0], RES_IN
-        self._activate(self.frames[-2], timer)
+        traced_info = {}
+        if self.traced:
+            # the camera frame, traceNewCoarse, insertFrame with the frame's image handed over on the device, the old
+            # points' residuals, activatePointsMT of the traced points into the window
+            self._set_frame(k, timer)
+            counts = self._trace(k, timer)
+            idx = timer.run("setup", ba.insertFrame, self._frame(k))
+            timer.run("setup", ba.set_frame_image_from, idx, self.img)
+            # the keyframe's DirPyr[0] in its tracer slot: the activation's residuals into it read it there
+            timer.run("setup", self.tracer.set_host_image_from, self.slot_of(k), self.img)
+            self.frames.append(k)
+            timer.run("setup", ba.addResidualsToNewest)
+            flagged = np.zeros(len(self.frames), np.int32)
+            if marginalize and len(self.frames) >= self.window:
+                flagged[0] = 1   # the frame this keyframe will marginalize
+            n_imm = self.tracer.n
+            act = self.last_activation = timer.run(
+                "activate", self.tracer.activate_into, ba, [self.slot_of(f) for f in self.frames], flagged,
+                self.currentMinActDist, None, True, None)
+            self.currentMinActDist = act["currentMinActDist"]
+            traced_info = dict(trace_counts=counts, n_immature=n_imm, n_activated=act["n_activated"],
+                               n_deleted=act["n_deleted"], act_handles=act["handles"],
+                               currentMinActDist=self.currentMinActDist, imm_dropped_with_frame=0)
+        else:
+            # insertFrame, new residuals of the old points, activation of the previous newest KF's points
+            self._insert_frame(k, timer)
+            timer.run("setup", ba.addResidualsToNewest)
+            for hd, st in self.last_state.items():
+                st[1], st[0] = st[0], RES_IN
+            self._activate(self.frames[-2], timer)
         timer.run("setup", ba.makeIDX)
         timer.run("setup", ba.synchronize)
         if check:
@@ -287,6 +432,8 @@ class KeyframeBA:
             timer.run("post", self.tracker.set_ref_ba, ba, self.image_path in ("device", "device_ptr"))
         # flagPointsForRemoval (Src/Mapping.cpp:248-328), the frame to marginalize: the oldest once the window is full
         info = dict(energies=energies, iters=n_it, n_points=ba.n_points, n_res=ba.n_res, dropped_points=len(gone))
+        info.update(traced_info)
+        new_traces_done = False
         if marginalize and self.frame_policy == "reference":
             # flagFramesForMarginalization decides (KfId = the sequence index; the newest keyframe's candidates are its
             # immature points), then flagPointsForRemoval and marginalizeFrame of every flagged frame
@@ -331,8 +478,13 @@ class KeyframeBA:
                 check(self, "points_marginalized")
             for hd in hd_all[marg | drop]:
                 self.cand_of.pop(int(hd), None)
+            if self.traced:  # makeNewTraces(fh) stands between flagPointsForRemoval and marginalizeFrame
+                info["n_keys"] = self._make_new_traces(k, timer, set_image=False)
+                new_traces_done = True
             timer.run("post", ba.removeFrame, marg_f, True)
-            self.frames.pop(marg_f)
+            gone_k = self.frames.pop(marg_f)
+            if self.traced:
+                info["imm_dropped_with_frame"] = self._drop_frame_points(gone_k, timer)
             if check:
                 check(self, "frame_marginalized")
             info.update(marginalized_points=int(marg.sum()), dropped=int(drop.sum()))
@@ -380,6 +532,8 @@ class KeyframeBA:
             if check:
                 check(self, "frame_marginalized")
             info.update(marginalized_points=int(marg.sum()), dropped=int(drop.sum()))
+        if self.traced and not new_traces_done:
+            info["n_keys"] = self._make_new_traces(k, timer, set_image=False)
         timer.run("post", ba.synchronize)
         info["wall_s"] = time.perf_counter() - wall0
         info["phase_s"] = dict(timer.t)

@@ -130,6 +130,38 @@ class ImmatureTracer:
         check(self.lib.hs_tracer_trace(self.h, len(hosts), ptr(hosts), ptr(c) if counts else None))
         return c if counts else None
 
+    # traceNewCoarse with a BAWindow as its window (hs_tracer_trace_ba)
+    def trace_ba(self, ba, slots, pose7, aff=(0.0, 0.0), exposure=1.0, counts=True):
+        """traceOn of every stored point against the frame set last, each host's (KRKi, Kt, aff) formed on the device
+        from ``ba``'s window frames (hslam_amd.ba.BAWindow, single-rank) and the new frame's worldToCam ``pose7``,
+        aff_g2l ``aff`` and ``exposure``.  slots: per window frame, the tracer host slot of its immature points.
+        Returns the six per-status counts, or None (and does not wait for the device) with counts=False."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        p = np.ascontiguousarray(pose7, np.float64)
+        a = np.ascontiguousarray(aff, np.float64)
+        assert p.shape == (7,) and a.shape == (2,)
+        c = np.zeros(6, np.int32)
+        check(self.lib.hs_tracer_trace_ba(self.h, ba.h, len(sl), ptr(sl), ptr(p), ptr(a), float(exposure),
+                                          ptr(c) if counts else None))
+        return c if counts else None
+
+    def trace_inputs(self):
+        """What the last trace_ba formed: [n_hosts, 14] float32 hs_trace_host records (KRKi | Kt | aff) indexed by
+        slot, as hs_tracer_trace takes them (hosts_array's layout)."""
+        n = C.c_int()
+        check(self.lib.hs_tracer_get_trace_inputs(self.h, C.byref(n), None))
+        out = np.zeros((n.value, 14), np.float32)
+        check(self.lib.hs_tracer_get_trace_inputs(self.h, None, ptr(out)))
+        return out
+
+    def trace_hosts(self, hosts, counts=True):
+        """hs_tracer_trace with ready hs_trace_host records ([n_hosts, 14] float32, e.g. trace_inputs())."""
+        h = np.ascontiguousarray(hosts, np.float32)
+        assert h.ndim == 2 and h.shape[1] == 14
+        c = np.zeros(6, np.int32)
+        check(self.lib.hs_tracer_trace(self.h, len(h), ptr(h), ptr(c) if counts else None))
+        return c if counts else None
+
     def set_scene(self, s):
         for i, img in enumerate(s.host_imgs):
             self.set_host_image(i, img)

@@ -23,6 +23,8 @@
  *   hs_tracer_activate_ba  the same call with a BA context (include/hs_ba.h) as its window, device to device: the
  *                          inputs from the window, the new MapPoints with their residuals (Src/Mapping.cpp:440-455,
  *                          Src/FullSystemOptPoint.cpp:142-169) into it, the immature points' removal on the device.
+ *   hs_tracer_trace_ba     traceNewCoarse with the same BA context as its window: each host's (KRKi, Kt, aff) formed on
+ *                          the device from the window's frames (Src/Mapping.cpp:500-513), then the same traceOn.
  *
  * Conventions as include/hs_ba.h: status codes (hs_types.h), caller-owned host buffers copied in/out,
  * the context owns device memory and its own HIP stream, single caller.  Images are Frame::DirPyr[0]:
@@ -167,6 +169,26 @@ int hs_tracer_compact_device(hs_tracer* t, const uint8_t* keep, const uint8_t* d
    set: HS_ERR_STATE once the window was committed again (ask before makeIDX). */
 int hs_tracer_get_act_inputs(hs_tracer* t, hs_ctx* ba, float K4[4], int* nF, hs_act_frame* frames, hs_act_pair* pairs,
                              int* n_active, int* act_frame, float* act_u, float* act_v, float* act_idepth);
+
+/* ---- tracing against a BA window --------------------------------------------------------------------------- */
+
+/* hs_tracer_trace whose hosts are the BA context's window frames (single-rank, same device, same image size): each
+   frame's (KRKi, Kt, aff) is formed on the device from its PRE_camToWorld, affine state and exposure in the window
+   and the new frame's pose / affine pair / exposure given here (Src/Mapping.cpp:500-513; K is the level-0 matrix),
+   written to the frame's slot, and every point is traced as hs_tracer_trace does.  The tracer's stream is ordered
+   behind the BA's by an event; counts6 == NULL returns without waiting for the device.
+     slots[nF]: per window frame (the window's current order), the tracer host slot of its immature points
+     new_worldToCam[7] (SE3 data as hs_frame's), new_aff_g2l[2] (a, b), new_ab_exposure: the frame being traced on
+   The frames are read where the last commit put them: pending removals (of frames or points) and point edits are
+   not committed by this call; a frame inserted since the last commit is, as by hs_tracer_activate_ba.
+   Errors leave both objects as they were: a multi-rank context, no frame set HS_ERR_STATE; another device, another
+   image size, nF != the window's frames, a slot out of range or named twice, a stored point on a slot that slots[]
+   does not name HS_ERR_INVALID. */
+int hs_tracer_trace_ba(hs_tracer* t, hs_ctx* ba, int nF, const int* slots, const double new_worldToCam[7],
+                       const double new_aff_g2l[2], float new_ab_exposure, int counts6[6]);
+/* what the last hs_tracer_trace_ba formed: *n_hosts = its largest slot + 1, hosts[*n_hosts] (nullable) indexed by
+   slot as hs_tracer_trace takes them; the slots of no window frame are zero */
+int hs_tracer_get_trace_inputs(hs_tracer* t, int* n_hosts, hs_trace_host* hosts);
 
 /* re-run the ImmaturePoint ctor on every point already added (same host / u / v, no upload): a fresh
    first-trace state (idepth_min 0, idepth_max NaN, quality 10000, IPS_UNINITIALIZED) */
