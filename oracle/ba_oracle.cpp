@@ -972,6 +972,14 @@ struct BA {
       int hIdx = CP + h * 8;
       for (int r = 0; r < 8; r++) for (int c = 0; c < 4; c++) H[c * n + hIdx + r] = H[(hIdx + r) * n + c];
     }
+    // The reference stops here, with frame-frame blocks that are NOT symmetric: accD[t1][t2] and accD[t2][t1]^T
+    // round (w L[r]) R[c] the other way round, ~5e-8 of sqrt(H_ii H_jj), and its LDLT then reads the lower triangle
+    // (Eigen::LDLT<MatXX, Lower>).  In exact arithmetic the two triangles are one matrix.  The project defines H_sc
+    // by its UPPER triangle, mirrored -- what the device's stitch writes -- so that the system the solve consumes,
+    // the one read back, and the device's are the same symmetric matrix (*Which triangle of
+    // H_sc*: a stated deviation from the reference at the rounding of H_sc's fp32 sums).
+    for (int r = 0; r < n; r++)
+      for (int c = r + 1; c < n; c++) H[c * n + r] = H[r * n + c];
   }
 
   // ------------------------------------------------------------ marginalization of points

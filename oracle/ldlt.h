@@ -17,6 +17,13 @@ inline void ldlt_solve(std::vector<double> A, int n, const std::vector<double>& 
   std::vector<int> transp(n);
   std::vector<double> temp(n);
   auto at = [&](int i, int j) -> double& { return A[i * n + j]; };
+  // Eigen::LDLT<MatrixXd> is LDLT<MatrixXd, Lower>: only the lower triangle is read.  The pivot swaps below move
+  // whole rows and columns, which carries upper-triangle entries into the lower triangle unless the two agree:
+  // mirror the lower triangle first.  (tests/test_solve_model.py held x to the lower triangle's solution and found
+  // such a mixture at 1e-7 while the Schur system still came with two fp32-different triangles; accumulateSC now
+  // hands over a symmetric one, and this keeps the solve well defined for any caller.)
+  for (int i = 0; i < n; i++)
+    for (int j = i + 1; j < n; j++) at(i, j) = at(j, i);
   for (int k = 0; k < n; k++) {
     int idx = k;
     double best = std::fabs(at(k, k));

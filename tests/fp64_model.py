@@ -201,7 +201,7 @@ def _ba_project(K, Th, Tt, x, y, idepth):
 def ba_systems(scene, active, state=None, idepth=None, idepth_zero=None, calib_value=None, huberTH=9.0,
                outlierTHSumComponent=2500.0, idepth_prior=None, step=1e-6, mutant=None):
     """The BA window's systems in hs_ba_get_system's layout (4 calibration + 8 per frame):
-    dict(HA, bA, Hsc, bsc, A_HA, A_bA, A_Hsc, A_bsc, n_terms).
+    dict(HA, bA, Hsc, bsc, A_HA, A_bA, A_Hsc, A_bsc, n_terms, and the point blocks Hfp [nP, dim], Hpp [nP], bp [nP]).
     scene: a BAScene (frames_eval, frames_state_zero, frames_exposure, pyramids, pt_*, res_*);
     active [n_res]: the residuals that are active and IN; state [nF, 10], idepth [n], calib_value [4] (unscaled,
     K = 50 * value): the current state (default: the scene's frames_state, pt_idepth and float32(K) / 50);
@@ -326,6 +326,8 @@ def ba_systems(scene, active, state=None, idepth=None, idepth_zero=None, calib_v
         np.add.at(bp, rp, gx[:, 20])
         pd = prior * (idp - idp0)
         bp = bp + (pd if sign else np.abs(pd))
+        if sign:   # the point blocks themselves (tests/solve_model.py's point step)
+            out["Hfp"], out["Hpp"], out["bp"] = Hfp, Hpp, bp
         has = Hpp > 0
         inv = np.where(has, 1.0 / np.where(has, Hpp, 1.0), 0.0)
         out[name + "Hsc"] = (Hfp * inv[:, None]).T @ Hfp
