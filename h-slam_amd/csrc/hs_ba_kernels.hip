@@ -1894,6 +1894,33 @@ __device__ __forceinline__ void panel_coop(const double a[4], double yr, int l, 
   }
   o.yr = yr;
 }
+// The main loop's panel: panel_coop's arithmetic, operation for operation, with only the outputs the loop uses.
+// One wave alone on its SIMD pays for every instruction it issues (DESIGN §4 Solve), so this form issues fewer:
+//  - lw (the carry, L D) goes out unmasked.  Only this lane's next rank-4 update reads it, and the entries on and
+//    above the diagonal belong to the diagonal rows, which are inert from the next phase on (never read by
+//    readlane, never stored);
+//  - the uniform factors stay local: a diagonal row's pivot is its own lw[l] (what the readlane of column l took
+//    from it), so the caller picks it from registers it already holds instead of the uniform copies.
+// ls keeps its row mask: L^T must stay zero on and above the diagonal, and the masked ls leaves a diagonal row's
+// rhs untouched after its own column, so the returned yr is that row's substituted rhs.
+__device__ __forceinline__ double panel_chain(const double a[4], double yr, int l, int base, double lw[4], double ls[4]) {
+  double pr[4] = {a[0], a[1], a[2], a[3]};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const double d = readlane_f64(pr[j], base + j);
+    const double dinv = rcp_f64(d);
+    const double ydj = readlane_f64(yr, base + j);
+    double q[4];
+#pragma unroll
+    for (int jp = j + 1; jp < 4; jp++) q[jp] = readlane_f64(pr[j], base + jp);
+    lw[j] = pr[j];
+    ls[j] = l > j ? pr[j] * dinv : 0.0;
+#pragma unroll
+    for (int jp = j + 1; jp < 4; jp++) pr[jp] = __builtin_fma(-(pr[j] * q[jp]), dinv, pr[jp]);
+    yr = __builtin_fma(-ls[j], ydj, yr);
+  }
+  return yr;
+}
 // a further (non-diagonal) row with the panel's factors: the same operations as panel_coop's lanes l >= 4
 __device__ __forceinline__ void panel_row_uniform(const double a[4], double yr, const Panel4& P, PanelOut& o) {
   double pr[4] = {a[0], a[1], a[2], a[3]};
@@ -2002,20 +2029,18 @@ __device__ __forceinline__ void ldlt_solve_blocked(const double* M, double* LT, 
 #pragma unroll
         for (int c = 0; c < 4; c++) a4[c] = __builtin_fma(-lwc[j], lsd[c][j], a4[c]);
       const int l = tid - 4 * k;  // row rw - K0 (< 0: a row of an earlier panel, inert)
-      Panel4 P;
-      PanelOut o;
-      panel_coop(a4, ycar, l, P, o, 4 * k);
+      double ls[4];
+      ycar = panel_chain(a4, ycar, l, 4 * k, lwc, ls);
       if (l >= 0 && tid + 4 < n) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) LT[(K0 + j) * LSTR + rw] = o.ls[j];  // zero on and above the diagonal
+        for (int j = 0; j < 4; j++) LT[(K0 + j) * LSTR + rw] = ls[j];  // zero on and above the diagonal
         if (l < 4) {
-          Dv[rw] = l == 0 ? P.d[0] : l == 1 ? P.d[1] : l == 2 ? P.d[2] : P.d[3];
-          yf[rw] = o.yr;
+          // the row's own pivot lwc[l], picked by the lane's two low bits (4 k is a multiple of 4: loop-invariant masks)
+          const double dlo = (tid & 1) ? lwc[1] : lwc[0], dhi = (tid & 1) ? lwc[3] : lwc[2];
+          Dv[rw] = (tid & 2) ? dhi : dlo;
+          yf[rw] = ycar;
         }
       }
-#pragma unroll
-      for (int j = 0; j < 4; j++) lwc[j] = o.lw[j];
-      ycar = o.yr;
       if (trace && tid == 0 && k == 4) trace[17] = clock64();
     } else if (tile && tc >= k + 2) {  // block k's rank-4 update of a trailing tile
       double lw[4][4], ls[4][4], dk[4];
