@@ -50,6 +50,7 @@ struct hs_flow : hs::Device {
   hs_flow_counts* h_counts = nullptr;  // pinned
   int n = 0;
   bool have_first = false, tracked = false;
+  long long first_id = 0;  // counts the first frames set
   float last_ms = 0;
   long long last_iters = 0;
 };
@@ -193,6 +194,7 @@ int finish_first(hs_flow* f, const uint8_t* d_src, int n) {
   f->n = n;
   f->have_first = true;
   f->tracked = false;
+  f->first_id++;
   if (f->last[0] < 2) f->last[0] = f->last[1] = -1;  // a track's pair is gone; a calc's pair has slots of its own
   return HS_OK;
 }
@@ -219,6 +221,18 @@ bool hs_flow_first_points(hs_flow* f, int* device, int* W, int* H, int* n, const
   *H = f->H;
   *n = f->n;
   *d_first = f->d_first;
+  return f->have_first;
+}
+
+bool hs_flow_tracked_keys(hs_flow* f, HsFlowKeys* k) {
+  k->device = f->device;
+  k->n = f->n;
+  k->first_id = f->first_id;
+  k->tracked = f->tracked;
+  k->first = f->d_first;
+  k->matched = f->d_pts[f->pcur];
+  k->good = f->d_good;
+  k->stream = f->stream;
   return f->have_first;
 }
 

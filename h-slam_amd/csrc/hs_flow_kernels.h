@@ -68,3 +68,18 @@ __global__ void hs_k_flow_lk(HsFlowLkArgs a);
 // (hs_refiner_set_points_flow does, for its violation count).
 struct hs_flow;
 bool hs_flow_first_points(hs_flow* f, int* device, int* W, int* H, int* n, const float2** d_first);
+
+// FirstFramePts, MatchedPts and MatchedStatus (n each) where the last hs_flow_track* left them on the device, for the
+// two-view fit (hs_twoview_fit_flow); false before the first frame.  first_id counts the hs_flow_set_first* calls, so a
+// consumer can tell whether two reads belong to one first frame.  `stream` is the flow's: a consumer on another stream
+// orders itself behind the last track with an event recorded there.  Only the next hs_flow_set_first* / _track*
+// rewrites the arrays, so a consumer waits for its own reads before it returns.
+struct HsFlowKeys {
+  int device, n;
+  long long first_id;
+  bool tracked;
+  const float2 *first, *matched;
+  const uint8_t* good;
+  hipStream_t stream;
+};
+bool hs_flow_tracked_keys(hs_flow* f, HsFlowKeys* k);

@@ -22,6 +22,7 @@
 #include "hs_init_kernels.h"
 #include "hs_init_rule.h"
 #include "hs_refine_kernels.h"
+#include "hs_twoview_kernels.h"
 
 namespace {
 // Eigen compute_inverse_size3 in double (CalibData: pyrKi[0] = pyrK[0].inverse(), Include/CalibData.h:150)
@@ -235,6 +236,48 @@ static int set_image(hs_refiner* r, hs_image* im, float4* hs_refiner::*dst, bool
   return HS_OK;
 }
 
+// the checks hs_refiner_set_points_flow makes of its flow context: its first frame's keys on the device
+static int flow_first_points(hs_refiner* r, hs_flow* f, int* n, const float2** d_first) {
+  int dev = 0, w = 0, h = 0;
+  if (!hs_flow_first_points(f, &dev, &w, &h, n, d_first))
+    return hs::fail(HS_ERR_STATE, "the flow holds no first frame (hs_flow_set_first)");
+  if (dev != r->device) return hs::fail(HS_ERR_INVALID, "flow and refiner are on different devices");
+  if (w != r->W || h != r->H) return hs::fail(HS_ERR_INVALID, "flow size differs from the refiner's");
+  if (*n <= 0) return hs::fail(HS_ERR_INVALID, "the flow's first frame has no points");
+  return HS_OK;
+}
+
+// the ctor's Pnt set-up from device arrays (enqueued on the refiner's stream or complete): keys, Triangulated, Pts3D.z
+static int points_from_device(hs_refiner* r, int n, const float2* d_first, const uint8_t* d_tri, const float* d_z) {
+  hs::Pool scratch;  // freed on every return path
+  int* d_bad = nullptr;
+  HS_TRY(scratch.alloc_zero(&d_bad, 1, r->stream));
+  HS_TRY(alloc_points(r, n));
+  hipStream_t s = r->stream;
+  HsRefPointsArgs a;
+  a.n = n;
+  a.W = r->W;
+  a.H = r->H;
+  a.n_planes = PF_COUNT;
+  a.pl_u = PF_U; a.pl_v = PF_V; a.pl_invz = PF_INVZ; a.pl_id = PF_ID; a.pl_idn = PF_IDN; a.pl_ir = PF_IR;
+  a.first = d_first;
+  a.tri = d_tri;
+  a.z = d_z;
+  a.pf = r->d_pf;
+  a.pb = r->d_pb;
+  a.n_bad = d_bad;
+  hipLaunchKernelGGL(hs_k_ref_points, dim3((n + 255) / 256), dim3(256), 0, s, a);
+  HS_HIP(hipGetLastError());
+  // the one read-back: the keys outside the image (also the wait after which tri / z / the flow's keys are free)
+  HS_HIP(hipMemcpyAsync(&r->h_flags[2], d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  if (r->h_flags[2] != 0) return hs::fail(HS_ERR_INVALID, "keypoint outside the image");  // r->n stays 0: no points
+  r->n = n;
+  r->jb_sel = 0;
+  r->last_iters = 0;
+  return HS_OK;
+}
+
 extern "C" {
 
 int hs_refiner_create(hs_refiner** out, int device_id, int width, int height, const double K4[4]) {
@@ -327,47 +370,34 @@ int hs_refiner_set_second_image(hs_refiner* r, hs_image* im, float ab_exposure) 
 
 int hs_refiner_set_points_flow(hs_refiner* r, hs_flow* f, const uint8_t* tri, const float* z) {
   if (!r || !f || !tri || !z) return hs::fail(HS_ERR_INVALID, "null argument");
-  int dev = 0, w = 0, h = 0, n = 0;
+  int n = 0;
   const float2* d_first = nullptr;
-  if (!hs_flow_first_points(f, &dev, &w, &h, &n, &d_first))
-    return hs::fail(HS_ERR_STATE, "the flow holds no first frame (hs_flow_set_first)");
-  if (dev != r->device) return hs::fail(HS_ERR_INVALID, "flow and refiner are on different devices");
-  if (w != r->W || h != r->H) return hs::fail(HS_ERR_INVALID, "flow size differs from the refiner's");
-  if (n <= 0) return hs::fail(HS_ERR_INVALID, "the flow's first frame has no points");
+  HS_TRY(flow_first_points(r, f, &n, &d_first));
   HS_HIP(hipSetDevice(r->device));
   hs::Pool scratch;  // freed on every return path
   uint8_t* d_tri = nullptr;
   float* d_z = nullptr;
-  int* d_bad = nullptr;
   HS_TRY(scratch.alloc(&d_tri, (size_t)n));
   HS_TRY(scratch.alloc(&d_z, (size_t)n));
-  HS_TRY(scratch.alloc_zero(&d_bad, 1, r->stream));
-  HS_TRY(alloc_points(r, n));
-  hipStream_t s = r->stream;
-  HS_HIP(hipMemcpyAsync(d_tri, tri, (size_t)n, hipMemcpyHostToDevice, s));
-  HS_HIP(hipMemcpyAsync(d_z, z, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-  HsRefPointsArgs a;
-  a.n = n;
-  a.W = r->W;
-  a.H = r->H;
-  a.n_planes = PF_COUNT;
-  a.pl_u = PF_U; a.pl_v = PF_V; a.pl_invz = PF_INVZ; a.pl_id = PF_ID; a.pl_idn = PF_IDN; a.pl_ir = PF_IR;
-  a.first = d_first;
-  a.tri = d_tri;
-  a.z = d_z;
-  a.pf = r->d_pf;
-  a.pb = r->d_pb;
-  a.n_bad = d_bad;
-  hipLaunchKernelGGL(hs_k_ref_points, dim3((n + 255) / 256), dim3(256), 0, s, a);
-  HS_HIP(hipGetLastError());
-  // the one read-back: the keys outside the image (also the wait after which tri / z / the flow's keys are free)
-  HS_HIP(hipMemcpyAsync(&r->h_flags[2], d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  HS_HIP(hipStreamSynchronize(s));
-  if (r->h_flags[2] != 0) return hs::fail(HS_ERR_INVALID, "keypoint outside the image");  // r->n stays 0: no points
-  r->n = n;
-  r->jb_sel = 0;
-  r->last_iters = 0;
-  return HS_OK;
+  HS_HIP(hipMemcpyAsync(d_tri, tri, (size_t)n, hipMemcpyHostToDevice, r->stream));
+  HS_HIP(hipMemcpyAsync(d_z, z, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, r->stream));
+  return points_from_device(r, n, d_first, d_tri, d_z);
+}
+
+int hs_refiner_set_points_twoview(hs_refiner* r, hs_flow* f, hs_twoview* tv) {
+  if (!r || !f || !tv) return hs::fail(HS_ERR_INVALID, "null argument");
+  int n = 0, tv_dev = 0, tv_n = 0;
+  const float2* d_first = nullptr;
+  const uint8_t* d_tri = nullptr;
+  const float* d_z = nullptr;
+  HS_TRY(flow_first_points(r, f, &n, &d_first));
+  const bool fresh = hs_twoview_triangulated(tv, f, &tv_dev, &tv_n, &d_tri, &d_z);
+  if (tv_dev != r->device) return hs::fail(HS_ERR_INVALID, "two-view fit and refiner are on different devices");
+  if (!fresh || tv_n != n)
+    return hs::fail(HS_ERR_STATE, "the two-view fit holds no successful fit of this flow's first frame and key count");
+  HS_HIP(hipSetDevice(r->device));
+  // the fit waited for its kernels before it returned: its arrays are complete, and this call waits for its reads
+  return points_from_device(r, n, d_first, d_tri, d_z);
 }
 
 int hs_refiner_get_videpth(hs_refiner* r, float* videpth) {

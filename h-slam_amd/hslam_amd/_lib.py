@@ -260,6 +260,18 @@ SIGNATURES = {
     "hs_refiner_set_points_flow": ([VP, VP, VP, VP], I),
     "hs_refiner_get_videpth": ([VP, VP], I),
     "hs_refiner_seed_ba": ([VP, VP, I, VP, VP, VP], I),
+    "hs_refiner_set_points_twoview": ([VP, VP, VP], I),
+    # include/hs_twoview.h
+    "hs_twoview_create": ([VP, I, I, VP], I),
+    "hs_twoview_destroy": ([VP], None),
+    "hs_twoview_fit": ([VP, I, VP, VP, VP, I, VP, VP], I),
+    "hs_twoview_fit_flow": ([VP, VP, I, VP, VP], I),
+    "hs_twoview_get": ([VP] * 8, I),
+    "hs_twoview_last_result": ([VP, VP], I),
+    "hs_twoview_get_rt": ([VP] * 8, I),
+    "hs_twoview_last_stats": ([VP, VP], I),
+    "hs_twoview_score_models": ([VP, I, VP, VP, I, VP], I),
+    "hs_twoview_check_rt": ([VP, I, VP, VP, VP], I),
     # include/hs_map.h
     "hs_map_create": ([VP, I, I], I),
     "hs_map_destroy": ([VP], None),

@@ -70,6 +70,12 @@ class DirectRefinement:
         check(self.lib.hs_refiner_set_points_flow(self.h, flow.h, ptr(t), ptr(zz)))
         self.n = len(t)
 
+    def set_points_twoview(self, flow, twoview):
+        """The same with tri / z read on the device from the last successful fit of a hslam_amd.twoview.TwoViewFit
+        (fit_flow on this flow's current first frame): z = mvIniP3D[i].z / median_depth."""
+        check(self.lib.hs_refiner_set_points_twoview(self.h, flow.h, twoview.h))
+        self.n = twoview.n
+
     def videpth(self):
         """Initializer::videpth as InitFromInitializer reads it: -1 untriangulated, the refined idepth where good,
         1 / z elsewhere."""

@@ -11,7 +11,7 @@
  * context owns its device memory and its own HIP stream, host buffers are the caller's and copied in / out, one
  * context per calling thread.  A call is complete on the device when it returns.
  *
- * Not built: the H/F RANSAC and the triangulation of Initializer::Initialize (host-sized, cv::SVD), MatchIndirect.
+ * Not built: MatchIndirect.  The H/F RANSAC and the triangulation of Initializer::Initialize are include/hs_twoview.h.
  *
  * Parity.  OpenCV is not a dependency of this project, so the contract below restates the scalar path of OpenCV 4's
  * calcOpticalFlowPyrLK for 8-bit single-channel input as arithmetic; tests/flow_ref.py states the same arithmetic in

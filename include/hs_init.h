@@ -7,6 +7,8 @@
  *                                                    image (include/hs_image.h) instead of two host W*H*3 arrays
  *   hs_refiner_set_points_flow                       the ctor's Pnt set-up (Src/Initializer.cpp:1362-1382) with
  *                                                    mvKeys read where the flow context holds them (FirstFramePts)
+ *   hs_refiner_set_points_twoview                    the same with vbTriangulated and mvIniP3D[i].z read where the two-view
+ *                                                    fit (include/hs_twoview.h) left them
  *   hs_refiner_get_videpth                           Initializer::videpth (Src/Initializer.cpp:155-159) after
  *                                                    DirectRefinement's write-back (:1393-1397)
  *   hs_refiner_seed_ba                               System::InitFromInitializer's point loop (Src/System.cpp:265-290)
@@ -15,8 +17,11 @@
  * buffers are the caller's and copied in / out, every entry checks device, size and state before any device call, and a
  * failed entry changes nothing unless its comment says otherwise.
  *
- * What stays on the host is Initializer::FindTransformation (the H / F RANSAC and the triangulation): it returns
- * vbTriangulated, mvIniP3D[i].z and the pose, which are this header's `triangulated`, `z` and hs_refiner_refine's pose.
+ * Initializer::FindTransformation (the H / F RANSAC and the triangulation) is include/hs_twoview.h: its vbTriangulated
+ * and mvIniP3D[i].z / MedianDepth reach the refiner device to device through hs_refiner_set_points_twoview, and its pose
+ * (R, t / MedianDepth of the result record) is hs_refiner_refine's start.  What stays with the caller is the cv::RNG draw
+ * of mvSets and the nmatches test of Src/Initializer.cpp:129-137, which reads the record's n_triangulated.  A caller with
+ * a fit of its own still hands `triangulated` and `z` to hs_refiner_set_points_flow.
  * The frames of the first window stay with the existing calls: frame 0 is hs_ba_insert_frame + hs_image_to_ba, the
  * second frame's pose is the refined Pose through hs_ba_insert_frame + hs_ba_add_residuals_to_newest.
  *
@@ -36,6 +41,7 @@
 #include "hs_flow.h"
 #include "hs_image.h"
 #include "hs_refine.h"
+#include "hs_twoview.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -58,6 +64,13 @@ int hs_refiner_set_second_image(hs_refiner* r, hs_image* im, float ab_exposure);
    violation the call returns HS_ERR_INVALID and the refiner holds no points.  Waits for the device (one 4-byte
    read-back: the violation count). */
 int hs_refiner_set_points_flow(hs_refiner* r, hs_flow* f, const uint8_t* triangulated, const float* z);
+
+/* hs_refiner_set_points_flow with `triangulated` and `z` taken device to device from the last fit of `tv`: z[i] =
+   mvIniP3D[i].z / median_depth (Src/Initializer.cpp:146-148).  The flow's rules are hs_refiner_set_points_flow's.
+   HS_ERR_STATE, nothing changed: the last fit of `tv` did not succeed (result.ok == 0, a refused call, or a debug entry
+   since), or it was not hs_twoview_fit_flow on this flow's current first frame and key count.  Another device:
+   HS_ERR_INVALID. */
+int hs_refiner_set_points_twoview(hs_refiner* r, hs_flow* f, hs_twoview* tv);
 
 /* Parity read-back, videpth[n]: -1 where the key is not triangulated; else the refined idepth where the point is
    good, 1 / z where it is not.  Before a refine this is the constructor's array (1 / z or -1).  Legal once points are
