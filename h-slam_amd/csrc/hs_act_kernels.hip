@@ -461,7 +461,6 @@ __global__ void __launch_bounds__(256) hs_k_act_dist(HsActDistArgs a) {
   constexpr int R = HS_ACT_BFS_STEPS - 1;
   const int w1 = a.w1, h1 = a.h1, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const bool itile = (int)blockIdx.x < a.n_tiles;
-  if (((a.dbg & 1) && !itile) || ((a.dbg & 2) && itile)) return;
   int x, y;
   bool live;
   if (itile) {  // 16 x 16 interior cells; wave wv: rows 4 wv .. 4 wv + 3
@@ -509,7 +508,7 @@ __global__ void __launch_bounds__(256) hs_k_act_dist(HsActDistArgs a) {
   }
   const int reach = itile ? R : R + 1;
   const int rx0 = bx0 - reach, rx1 = bx1 + reach, ry0 = by0 - reach, ry1 = by1 + reach;
-  const int ns = (a.dbg & 4) ? 0 : *a.n_seeds;
+  const int ns = *a.n_seeds;
   int* wt = reinterpret_cast<int*>(wtile[wv]);
   for (int t0 = 0; t0 < ns; t0 += 1024) {
     const int tn = min(1024, ns - t0);

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "hs_ba_ctx.h"
+#include "hs_env.h"
 
 using namespace hs;
 
@@ -35,19 +36,6 @@ void drop_graph(hs_ctx* c) {
   if (c->gexec) (void)hipGraphExecDestroy(c->gexec);
   c->gexec = nullptr;
   c->graph_hdif = nullptr;
-}
-
-// upper bound of the linearize blocks of any window of at most capP points (make_partition below): every host's
-// points split into blocks of bw * ppw points, ppw chosen so the grid stays near the target; env HS_LIN_PPW forces a
-// ppw (more blocks), HS_ACC_EXACT one block per host
-int max_blocks_for(int capP) {
-  int m = std::max(kLinBlocksTarget, kLin8BlocksTarget) + HS_MAXF;
-  if (const char* e = std::getenv("HS_LIN8_BLOCKS")) m = std::max(m, std::atoi(e) + HS_MAXF);
-  if (const char* e = std::getenv("HS_LIN_PPW")) {
-    const int ppw = std::max(1, std::atoi(e));
-    m = std::max(m, capP / (HS_LIN_NW * ppw) + 1 + HS_MAXF);
-  }
-  return m;
 }
 
 static void free_buffers(hs_ctx* c) {
@@ -219,8 +207,7 @@ int ensure_capacity(hs_ctx* c, int W, int H, int capP, int capBlk) {
   c->n_dev_staged = 0;
   HS_TRY(c->cap.pinned(&c->h_raw, npx));
   HS_TRY(dalloc(&c->d_raw, npx));
-  const char* tr = std::getenv("HS_KTRACE");
-  c->tracing = tr && tr[0] == '1';
+  c->tracing = env::ktrace();
   if (c->tracing) {
     HS_TRY(dalloc(&c->d_tr_lin, (size_t)capBlk * 16));
     HS_TRY(dalloc(&c->d_tr_acc, (size_t)(HS_MAXF * ((ne * 64 + 255) / 256) + 1 + 64) * 16));
@@ -371,36 +358,33 @@ int pack_slot(hs_ctx* c, int s) {
 }
 
 // hs_k_lin partitioning of the committed window (host_pt_begin).  Production: every host's points are split into
-// blocks of HS_LIN_NW waves x ppw points (ppw grows with the window so the grid stays near kLinBlocksTarget blocks;
-// env HS_LIN_PPW overrides).  HS_ACC_EXACT=1: one block per host whose wave 0 takes every point in order = the
+// blocks of HS_LIN_NW waves x ppw points (ppw grows with the window so the grid stays near kLinBlocksTarget
+// blocks).  HS_ACC_EXACT=1: one block per host whose wave 0 takes every point in order = the
 // single-thread reference's fp32 accumulator sums (no shiftUp emulation: at most 1000 points per host).
 int make_partition(hs_ctx* c) {
   const int nF = c->nF, nP = c->nP;
-  const char* ex = std::getenv("HS_ACC_EXACT");
-  c->exact = ex && ex[0] == '1';
+  c->exact = env::acc_exact();
   c->ne = hs_ne(c->exact);
   c->Q = (c->ne * 64 + 255) / 256;
   c->blk_begin.assign(nF + 1, 0);
-  c->lin8 = !c->exact && nP >= kLin8MinPoints;
-  if (const char* e = std::getenv("HS_LIN8")) c->lin8 = !c->exact && e[0] == '1';
+  c->lin8 = !c->exact && env::lin8(nP >= kLin8MinPoints);
   c->lin8 = c->lin8 && lin8_supported(c->cap_W, c->cap_H);  // its 32-bit tap offsets
   // the extra launch of pass 3 costs more than a one-block scan of a small window's candidates
-  c->th_multi = nP >= kThMultiMinPoints;
-  if (const char* e = std::getenv("HS_TH_MULTI")) c->th_multi = e[0] == '1';
+  c->th_multi = env::th_multi(nP >= kThMultiMinPoints);
+  c->lin8_hist = env::lin8_hist();
+  c->graph = env::graph();
+  c->host_break = env::host_break();
   // points per block: hs_k_lin HS_LIN_NW waves x ppw points; hs_k_lin8 HS_LIN8_NT / 64 = 8 waves x ppw groups of 8
   // points (its partition also serves hs_k_lin's marginalization / linearizeAll(true) passes, with W = 8 waves)
   const int bw = c->lin8 ? (HS_LIN8_NT / 64) * 8 : HS_LIN_NW;
-  int target = c->lin8 ? kLin8BlocksTarget : kLinBlocksTarget;
-  if (const char* e = std::getenv("HS_LIN8_BLOCKS"); e && c->lin8) target = std::max(1, std::atoi(e));
-  int ppw = std::max(1, (nP + bw * target - 1) / (bw * target));
-  const char* pe = std::getenv("HS_LIN_PPW");
-  if (pe) ppw = std::max(1, std::atoi(pe));
+  const int target = c->lin8 ? kLin8BlocksTarget : kLinBlocksTarget;
+  const int ppw = std::max(1, (nP + bw * target - 1) / (bw * target));
   // hs_k_lin8 with more than one point group per wave: every CU a block.  ceil(nh / (bw ppw)) blocks per host leave
   // CUs idle (200k points: 31 per host, 248 of 256) and rotate the host's image bands over the XCDs from host to host
-  // (workgroup w runs on XCD w mod 8); floor(target nh / nP) blocks per host fill the grid (Σ <= target + nF, within
-  // the block capacity) and, at 32 per host, give XCD x the same bands q = x mod 8 of every host (its L2 holds them):
-  // 200k 160 -> 137 us per launch (hs_k_lin8 round 6)
-  const bool fill = c->lin8 && ppw > 1 && !pe && !std::getenv("HS_LIN8_BLOCKS") && !std::getenv("HS_LIN8_NOFILL");
+  // (workgroup w runs on XCD w mod 8); floor(target nh / nP) blocks per host fill the grid (Σ <= target + nF =
+  // kMaxLinBlocks, the block capacity) and, at 32 per host, give XCD x the same bands q = x mod 8 of every host (its
+  // L2 holds them): 200k 160 -> 137 us per launch (hs_k_lin8 round 6)
+  const bool fill = c->lin8 && ppw > 1 && !env::lin8_nofill();
   c->W = c->exact ? 1 : (c->lin8 ? HS_LIN8_NT / 64 : HS_LIN_NW);
   for (int h = 0; h < nF; h++) {
     const int nh = c->host_pt_begin[h + 1] - c->host_pt_begin[h];
@@ -469,11 +453,9 @@ static int launch_linearize(hs_ctx* c, int fuse, bool marg = false, bool accumul
   a.p_JpJdF = c->d_p_JpJdF; a.p_step = c->d_p_step;
   a.fix_relBL = c->d_fix_relBL; a.fix_nGood = c->d_fix_nGood;
   a.newest_cand = c->d_cand + (size_t)c->rank * c->cand_stride;
-  // large single-rank windows: hs_k_lin8 counts setNewFrameEnergyTH's pass-1 histogram itself (env HS_LIN8_HIST=0:
+  // large single-rank windows: hs_k_lin8 counts setNewFrameEnergyTH's pass-1 histogram itself (HS_LIN8_HIST=0:
   // hs_k_reduce's histogram blocks, as before)
-  const char* lh = std::getenv("HS_LIN8_HIST");
-  const bool lin_hist = c->lin8 && !marg && !fix && accumulate && c->th_multi && !c->multi_rank() &&
-                        !(lh && lh[0] == '0');
+  const bool lin_hist = c->lin8 && !marg && !fix && accumulate && c->th_multi && !c->multi_rank() && c->lin8_hist;
   a.th_hist = lin_hist ? c->d_th_hist : nullptr;
   c->hist_in_lin = lin_hist;
   a.part = c->d_part; a.part_e = c->d_part_e;
@@ -631,11 +613,10 @@ static int launch_reduce(hs_ctx* c, bool skip_threshold = false, bool sep = fals
   HS_HIP(hipGetLastError());
   if (multi) {  // pass 3: the select over pass 2's histogram and survivors.  It only feeds the next linearize: in the
                 // fused GN loop it runs as block 1 of the next solve launch, beside the solve (defer), else as a
-                // one-block launch now (env HS_TH_BESIDE=0: always the launch)
+                // one-block launch now
     // (not under the device-side break: a launch after the break would rerun pass 3 on the consumed histograms,
     // where hs_k_th_select's own launch returns at entry)
-    const char* tb = std::getenv("HS_TH_BESIDE");
-    if (defer && !c->brk_active && !(tb && tb[0] == '0')) {
+    if (defer && !c->brk_active) {
       c->gath_th = 2;
     } else {
       hipLaunchKernelGGL(hs_k_th_select, dim3(1), dim3(HS_STITCH_NT), 0, c->stream, a);
@@ -701,7 +682,6 @@ static int launch_solve(hs_ctx* c, int flags, int iteration, bool log) {
   a.minOpt = c->P.minOptIterations;
   a.chk_adj = 1;
   a.adj_expect = c->d_ticket + 1;
-  if (const char* e = std::getenv("HS_SOLVE_DBG")) a.dbg = std::atoi(e);
   hipLaunchKernelGGL(hs_k_solve, dim3(grid), dim3(HS_SOLVE_NT), 0, c->stream, a);
   HS_HIP(hipGetLastError());
   c->h_state_valid = false;
@@ -803,12 +783,11 @@ static int dump_traces(hs_ctx* c) {
   const double tick_us = khz > 0 ? 1e3 / khz : 0.01;
   long long f[4] = {0, 0, 0, 0}, l[4] = {0, 0, 0, 0};
   HS_TRY(dump_one("solve", c->d_tr_solve, 1, tick_us, c->stream, &f[0], &l[0]));
-  {  // in-loop shader-clock stamps of the solve (slots 16..23, cycles after slot 16)
+  {  // in-loop shader-clock stamps of the solve's panel k = 4 (slots 16..19, cycles after slot 16)
     long long h[32];
     HS_HIP(hipMemcpy(h, c->d_tr_solve, sizeof(h), hipMemcpyDeviceToHost));
     std::fprintf(stderr, "[hs trace] solve kb4 cycles:");
-    for (int k = 17; k < 30; k++)
-      if (k < 24 || k > 25) std::fprintf(stderr, " s%d=%lld", k, h[k] ? h[k] - h[16] : -1);
+    for (int k = 17; k < 20; k++) std::fprintf(stderr, " s%d=%lld", k, h[k] ? h[k] - h[16] : -1);
     std::fprintf(stderr, "\n");
   }
   HS_TRY(dump_one("linearize", c->d_tr_lin, c->nblk, tick_us, c->stream, &f[1], &l[1], &c->blk_begin));
@@ -834,13 +813,11 @@ static int gn_iterations(hs_ctx* c, int it0, int K, bool allow_break, double* en
   const bool all = c->events >= 2;
   // hipGraph replay of iteration pairs: no per-iteration host work (no break test, no events, no tracing, no
   // collectives inside a capture)
-  const char* ge = std::getenv("HS_GRAPH");
-  const bool graph = (ge && ge[0] == '1') && !allow_break && nev == 0 && !c->tracing && !c->multi_rank() && K >= 2;
+  const bool graph = c->graph && !allow_break && nev == 0 && !c->tracing && !c->multi_rank() && K >= 2;
   // allow_break on one rank: the break test runs on the device (hs_k_solve), so the K iterations are enqueued with
   // no host round trip between them; launches after the break return at entry.  Multi-rank windows, tracing and
   // HS_HOST_BREAK=1 read canbreak back after every iteration instead.
-  const char* hb = std::getenv("HS_HOST_BREAK");
-  const bool dev_brk = allow_break && !c->multi_rank() && !c->tracing && !(hb && hb[0] == '1');
+  const bool dev_brk = allow_break && !c->multi_rank() && !c->tracing && !c->host_break;
   // before any capture: launch_solve must not sync inside one
   if (c->tail_pending || c->proj_stale) HS_TRY(settle_projector(c));
   HS_TRY(set_loop_counters(c, it0, !graph));
@@ -1080,8 +1057,7 @@ int hs_create(hs_ctx** out, const hs_params* params, int device_id) {
   hs_ctx* c = new hs_ctx();
   if (params) c->P = *params;
   else hs_params_default(&c->P);
-  const char* ev = std::getenv("HS_EVENT_TIMING");
-  c->events = ev ? std::atoi(ev) : 0;
+  c->events = env::event_timing();
   const int rc = [&]() -> int {
     HS_TRY(c->open(device_id));
     HS_TRY(c->pool.pinned(&c->h_state, 1));
@@ -1188,7 +1164,7 @@ int hs_ba_set_window(hs_ctx* c, const hs_camera* cam, int nF, const hs_frame* fr
   int stride = nP;
   HS_TRY(cand_stride_for(c, nP, &stride));
   const int needP = std::max(nP, stride);
-  HS_TRY(ensure_capacity(c, cam->width, cam->height, needP, max_blocks_for(needP)));
+  HS_TRY(ensure_capacity(c, cam->width, cam->height, needP, kMaxLinBlocks));
   c->cam = *cam;
   c->haveCam = true;
   c->incremental = false;

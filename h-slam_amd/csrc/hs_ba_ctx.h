@@ -37,6 +37,11 @@ constexpr int kLinBlocksTarget = 256;  // linearize blocks of a window (points p
 constexpr int kLin8MinPoints = 4000;
 constexpr int kThMultiMinPoints = 60000;  // the multi-block threshold select (below: one block beside the solve)
 constexpr int kLin8BlocksTarget = 256;  // hs_k_lin8 blocks of a window (one 8-wave block per CU)
+// upper bound of the linearize blocks of any window (make_partition): a host's nh of the nP points take
+// ceil(nh / (bw ppw)) blocks with bw ppw >= nP / target, and hs_k_lin8's grid fill raises that to at most
+// floor(target nh / nP): either way at most target nh / nP + 1 per host, target + nF over the window.  HS_ACC_EXACT:
+// one block per host, nF.
+constexpr int kMaxLinBlocks = (kLinBlocksTarget > kLin8BlocksTarget ? kLinBlocksTarget : kLin8BlocksTarget) + HS_MAXF;
 // hs_k_lin8's taps address the packed slots through one buffer resource with 32-bit offsets: the texel index is formed
 // by 24-bit multiplies (W * H < 2^23) and slot * W * H * 12 + offset must stay below 2^31 over all HS_MAXF slots.
 // Larger images run hs_k_lin (64-bit addressing) at every point count.
@@ -113,6 +118,9 @@ struct hs_ctx : hs::Device {
   // one-block pass 3 over pass 2's survivors, instead of the stitch's single select block scanning every candidate
   // twice (env HS_TH_MULTI=0 / 1 forces it off / on)
   bool th_multi = false;
+  // the commit's other switches (hs_env.h): hs_k_lin8 counts the select's pass-1 histogram; the GN loop replays a
+  // captured graph; the GN loop's break test runs on the host
+  bool lin8_hist = true, graph = false, host_break = false;
   bool hist_in_lin = false;       // the last linearize launch counted the select's pass-1 histogram (hs_k_lin8)
   bool sepValid = false;          // d_sep holds the separate HA / HSC of the last linearization
   std::vector<int> pt_host, res_point, res_target, host_pt_begin;
@@ -313,7 +321,6 @@ int mirror_points(hs_ctx* c);     // points the mirror holds (committed and stag
 int seed_frame_check(hs_ctx* c, int frame);
 int stage_seeded(hs_ctx* c, int n, int frame, int* handles_out);
 inline int commit_if_dirty(hs_ctx* c) { return c->dirty ? commit(c) : HS_OK; }
-int max_blocks_for(int capP);
 // everything enqueued on the context's stream has finished: hipStreamSynchronize on a single-rank context; on a
 // multi-rank one a bounded poll of the stream and the communicator's asynchronous error (HS_ERR_RCCL + abort on a
 // failure or after comm_timeout_ms)

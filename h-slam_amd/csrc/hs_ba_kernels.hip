@@ -1956,7 +1956,7 @@ __device__ __forceinline__ void panel_row_store(const PanelOut& o, const Panel4&
 }
 
 __device__ __forceinline__ void ldlt_solve_blocked(const double* M, double* LT, double* W, double* yv, int n, int tid,
-                                                   long long* trace, int dbg = 0) {
+                                                   long long* trace) {
   constexpr int MD = HS_MAXDIM;
   static_assert((HS_MAXDIM / 4 - 2) * (HS_MAXDIM / 4 - 1) / 2 <= SOLVE_NT - 64, "one trailing tile per lane");
   static_assert(LSTR % 2 == 0, "16 B aligned LT groups");
@@ -2344,18 +2344,12 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
     // factorization is backward stable without pivoting; Eigen's LDLT (Src/EnergyFunctional.cpp:801) pivots on
     // the diagonal, which changes x by rounding only (the LDLT is parity-unpinned; tests bound x by
     // the reference's own 1- vs 8-thread spread)
-    if ((a.dbg & 8) && a.trace && tid == 0) a.trace[20] = clock64();
-    for (int rep = 0; rep < ((a.dbg & 8) ? 2 : 1); rep++) {
-      ldlt_solve_blocked(A, LT, B, yv, n, tid, a.trace, a.dbg);
-      __syncthreads();
-      if ((a.dbg & 8) && a.trace && tid == 0) a.trace[21 + rep] = clock64();
-    }
+    ldlt_solve_blocked(A, LT, B, yv, n, tid, a.trace);
     __syncthreads();
     HS_TRACE(a, 3);
     if (tid < n) xs[tid] = Sv[tid] * yv[tid];
     __syncthreads();
     HS_TRACE(a, 4);
-    if ((a.dbg & 32) && a.trace && tid == 0) a.trace[26] = clock64();
     // xAd (EnergyFunctional::resubstituteF_MT's per-pair adjoint products) for the granular path only: in the
     // fused GN loop (HS_APPLY) the linearize kernel forms its host's xAd itself from lastX.  The fp32 adjoints
     // are requested here so their latency overlaps orthogonalize.
@@ -2400,7 +2394,6 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
         if (part == 0) tk[d] = sacc;
       }
       __syncthreads();
-      if ((a.dbg & 32) && a.trace && tid == 0) a.trace[27] = clock64();
     }
     // resubstituteF_MT: frame / calib steps, xAd, cstep; row q's thread first applies its own orthogonalize
     // update (x_q -= (P x)_q), so no barrier separates the two
@@ -2428,7 +2421,6 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
       st->frames[tid].step[9] = 0;
     }
     __syncthreads();
-    if ((a.dbg & 32) && a.trace && tid == 0) a.trace[28] = clock64();
     if (tid < 4) st->cstep[tid] = xF[tid];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
@@ -2443,7 +2435,6 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
         a.xAd[o] = s1 + s2;
       }
     }
-    if ((a.dbg & 32) && a.trace && tid == 0) a.trace[29] = clock64();
     HS_TRACE(a, 5);
   }
   __syncthreads();
@@ -2458,7 +2449,6 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
     double cv[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) cv[q] = st->calib.value[q] + 1.0f * st->calib.step[q];
-    if ((a.dbg & 16) && a.trace && tid == 0) a.trace[20] = clock64();
     // stage 1 on wave 1 (lane 64 + f): frame f's new pose into LDS; its write-back waits until after the barrier,
     // beside wave 0's pair stage
     const int fw = tid - 64;
@@ -2513,9 +2503,7 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
       ext = st->frames[tt].ab_exposure;
       sz7 = st->frames[hh].state_zero[7];
     }
-    if ((a.dbg & 16) && a.trace && tid == 0) a.trace[22] = clock64();
     __syncthreads();
-    if ((a.dbg & 16) && a.trace && tid == 0) a.trace[23] = clock64();
     if (tid == 192) {  // the calib on wave 3, beside the pair stage (every lane read cv before the barrier)
       hs::CalibH& cal = st->calib;
 #pragma unroll
@@ -2543,7 +2531,6 @@ __global__ __launch_bounds__(SOLVE_NT) void hs_k_solve(HsSolveArgs a) {
         F.delta_prior[q] = ns[q] - 0.0;
       }
     }
-    if ((a.dbg & 16) && a.trace && tid == 0) a.trace[21] = clock64();
     HS_TRACE(a, 6);
     if (tid == 0) HS_TRACE(a, 10);
   }

@@ -335,7 +335,7 @@ int hs_ba_reserve(hs_ctx* c, const hs_camera* cam, int max_points) {
   if (cam->width < 8 || cam->height < 8 || max_points < 1) return fail(HS_ERR_INVALID, "bad camera size / capacity");
   HS_HIP(hipSetDevice(c->device));
   HS_TRY(wait_stream(c));
-  HS_TRY(ensure_capacity(c, cam->width, cam->height, max_points, max_blocks_for(max_points)));
+  HS_TRY(ensure_capacity(c, cam->width, cam->height, max_points, kMaxLinBlocks));
   drop_graph(c);
   c->cam = *cam;
   c->haveCam = true;

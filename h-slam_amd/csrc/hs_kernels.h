@@ -220,7 +220,6 @@ struct HsSolveArgs {
   long long* trace;
   double initialCalibHessian;
   float thOptIterations;
-  int dbg;                     // experiments (env HS_SOLVE_DBG); 0 in production
   // multi-rank exchange (hs_ba.cpp exchange()): gsys = [nranks][gstride] the ranks' system vectors + energies as
   // all-gathered, summed here in rank order (every rank the same sums) in place of sys / sysE; sys_out receives the
   // sum.  th_local: the launch's block 1 runs setNewFrameEnergyTH's select over the gathered candidates (th): 1 the

@@ -16,6 +16,7 @@
 #include "../../include/hs_init.h"
 #include "../../include/hs_refine.h"
 #include "hs_ba_ctx.h"
+#include "hs_env.h"
 #include "hs_flow_kernels.h"
 #include "hs_host.h"
 #include "hs_image_kernels.h"
@@ -64,7 +65,8 @@ struct hs_refiner : hs::Device {
   int* d_ticket = nullptr;
   float* d_log = nullptr;
   int last_iters = 0;
-  long long* d_trace = nullptr;  // HS_REF_TRACE=1: per-block stamps of each step launch, dumped to stderr
+  bool tracing = false;          // HS_KTRACE=1 at creation
+  long long* d_trace = nullptr;  // tracing: per-block stamps of each step launch, dumped to stderr
   double last_ms = 0;
   // hs_refiner_seed_ba (allocated by its first call, regrown with the point count)
   int seed_cap = 0;
@@ -216,7 +218,7 @@ static int alloc_points(hs_refiner* r, int n) {
   HS_TRY(m.alloc(&r->d_pf, PF_COUNT * (size_t)n));
   HS_TRY(m.alloc(&r->d_pb, 3 * (size_t)n));
   HS_TRY(m.alloc(&r->d_part, HS_REF_NRED * nb));
-  if (const char* e = std::getenv("HS_REF_TRACE"); e && std::atoi(e) > 0) HS_TRY(m.alloc_zero(&r->d_trace, 16 * nb, r->stream));
+  if (r->tracing) HS_TRY(m.alloc_zero(&r->d_trace, 16 * nb, r->stream));
   return HS_OK;
 }
 
@@ -287,6 +289,7 @@ int hs_refiner_create(hs_refiner** out, int device_id, int width, int height, co
   hs_refiner* r = new hs_refiner();
   r->W = width;
   r->H = height;
+  r->tracing = hs::env::ktrace();
   for (int q = 0; q < 4; q++) r->K4[q] = K4[q];
   const double K[9] = {K4[0], 0, K4[2], 0, K4[1], K4[3], 0, 0, 1};
   inv3d(K, r->Ki);

@@ -31,6 +31,7 @@
 #include <cfloat>
 
 #include "hs_interp.h"
+#include "hs_kernels.h"
 #include "hs_refine_kernels.h"
 
 namespace {
@@ -61,11 +62,6 @@ __device__ __forceinline__ float dot8(const float* a, const float* b) {
   for (int l = 0; l < 4; l++) s[l] = a[l] * b[l] + a[l + 4] * b[l + 4];
   return (s[0] + s[2]) + (s[1] + s[3]);
 }
-
-#define REF_TRACE(slot)                                                                        \
-  do {                                                                                         \
-    if (a.trace && threadIdx.x == 0) a.trace[(size_t)blockIdx.x * 16 + (slot)] = wall_clock64(); \
-  } while (0)
 
 // thread 0's LDS workspace for the LM step (dynamically indexed arrays in private memory would live in scratch)
 struct RefWork {
@@ -163,9 +159,9 @@ __device__ __forceinline__ void lm_solve_prep(const HsRefArgs& a, const HsRefCtl
 // tail (thread 0): the 6x6 LDLT, inc, Tn = exp(inc) * T, affn and the constants of the pass at Tn
 __device__ __forceinline__ void lm_solve_tail(const HsRefArgs& a, HsRefCtl* C, RefWork* W) {
   const float wM[6] = {1.0f, 1.0f, 1.0f, 0.5f, 0.5f, 0.5f};
-  REF_TRACE(11);
+  HS_TRACE(a, 11);
   ldlt6f_solve(W->H6, W->bl, W->x6);  // fixAffine = true
-  REF_TRACE(12);
+  HS_TRACE(a, 12);
   double incd[6];
 #pragma unroll
   for (int k = 0; k < 6; k++) {
@@ -183,11 +179,11 @@ __device__ __forceinline__ void lm_solve_tail(const HsRefArgs& a, HsRefCtl* C, R
   double affn[2] = {C->aff[0] + C->inc[6], C->aff[1] + C->inc[7]};
   C->affn[0] = affn[0];
   C->affn[1] = affn[1];
-  REF_TRACE(13);
+  HS_TRACE(a, 13);
   HsRefPass pc;
   hs_ref_pass_consts(Tn, affn, a.Ki, a.n, &pc);
   C->pc = pc;
-  REF_TRACE(14);
+  HS_TRACE(a, 14);
 }
 
 enum { LM_COPY = 1, LM_SOLVE = 2, LM_OUT = 4 };
@@ -235,7 +231,7 @@ __device__ __forceinline__ int lm_decide(const HsRefArgs& a, HsRefCtl* C, RefWor
     C->done = 0;
     return LM_COPY | LM_SOLVE;
   }
-  REF_TRACE(9);
+  HS_TRACE(a, 9);
   // HS_REF_ITER: calcEC + the accept test (Src/Initializer.cpp:1470-1540)
   const int it = C->iteration;
   const float reg0 = C->snapped ? ec[0] : 0.f, reg1 = C->snapped ? ec[1] : 0.f;
@@ -278,7 +274,7 @@ __device__ __forceinline__ int lm_decide(const HsRefArgs& a, HsRefCtl* C, RefWor
     return cp;
   }
   C->iteration = it + 1;
-  REF_TRACE(10);
+  HS_TRACE(a, 10);
   return cp | LM_SOLVE;
 }
 
@@ -358,7 +354,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
   const bool valid = i < n;
   const bool leader = k == 0;
   const HsRefPoints& P = a.p;
-  REF_TRACE(0);
+  HS_TRACE(a, 0);
   // every lane's point coordinates, issued before the control-block round trip
   float pu = 0.f, pv = 0.f;
   int tri = 0;
@@ -384,7 +380,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
     S.ctl.jb_sel = a.jb_sel0;
   }
   __syncthreads();
-  REF_TRACE(1);
+  HS_TRACE(a, 1);
   const int sel = S.ctl.jb_sel ^ S.ctl.apply_prev;  // JbBuffer plane after this launch's applyStep
   float* __restrict__ Jbn = P.jb[sel ^ 1];
   // ---- prologue (the point's leader lane): every load first (the arrays may alias as far as the compiler
@@ -457,7 +453,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
     }
   }
   if (mode == HS_REF_FINAL) return;
-  REF_TRACE(2);
+  HS_TRACE(a, 2);
   const int base = lane & ~7;
   idn = __shfl(idn, base);
   g = __shfl(g, base);
@@ -470,7 +466,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
   const unsigned int fb = (unsigned int)(failm >> base) & 0xffu;
   const int f = fb ? __builtin_ctz(fb) : 8;  // first failing pixel: the reference's loop breaks there
   __syncthreads();
-  REF_TRACE(3);
+  HS_TRACE(a, 3);
   float E = 0.f, ec0 = 0.f, ec1 = 0.f;
   float* prow = S.Pl[slot];
   if (valid && leader) {
@@ -540,7 +536,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
     for (int q = 0; q < 13; q++) prow[q] = 0.f;
   }
   __syncthreads();
-  REF_TRACE(4);
+  HS_TRACE(a, 4);
   {  // this lane's acc9 row (zero unless its point is good)
     const bool pg = S.pgood[slot] != 0;
 #pragma unroll
@@ -585,7 +581,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
     }
     __hip_atomic_store(&a.part[(size_t)blockIdx.x * HS_REF_NRED + tid], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  REF_TRACE(5);
+  HS_TRACE(a, 5);
   // hand-off (HIP memory model, no reliance on write-through behaviour): every thread's partial store is ordered
   // before the ticket by an agent-scope release fence, the ticket is an acq_rel read-modify-write, and the block
   // whose add returns nblocks - 1 takes an agent-scope acquire fence before it reads the other blocks' partials
@@ -595,7 +591,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
   if (tid == 0)
     S.last = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == a.nblocks - 1;
   __syncthreads();
-  REF_TRACE(6);
+  HS_TRACE(a, 6);
   if (!S.last) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   if (tid < HS_REF_NRED) {  // block order, up to 64 independent write-through loads in flight per thread
@@ -627,7 +623,7 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
   }
   __syncthreads();
   if (tid == 0) {
-    REF_TRACE(8);
+    HS_TRACE(a, 8);
     const HsRefPass pc = S.ctl.pc;
     S.lmflags = lm_decide(a, &S.ctl, &S.wk, S.red, pc, sel);
   }
@@ -665,5 +661,5 @@ __global__ __launch_bounds__(RB) void hs_k_refine_step(HsRefArgs a) {
     uint2* gs = reinterpret_cast<uint2*>(a.ctl);
     for (int w = tid; w < CW; w += RB) gs[w] = ls[w];
   }
-  REF_TRACE(7);
+  HS_TRACE(a, 7);
 }

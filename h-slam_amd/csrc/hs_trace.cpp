@@ -13,6 +13,7 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_trace.h"
 #include "hs_ba_ctx.h"
+#include "hs_env.h"
 #include "hs_host.h"
 #include "hs_trace_kernels.h"
 #include "../../include/hs_undist.h"
@@ -46,6 +47,7 @@ struct hs_tracer : hs::Device {
   float last_ms = 0;
   long long last_steps = 0;
   bool stats_pending = false;
+  bool tracing = false;  // HS_KTRACE=1 at creation: hs_k_act_select's profile on stderr
   int max_host = -1;  // largest host slot of the stored points
   float* d_type = nullptr;  // ImmaturePoint::my_type
   // point activation scratch (allocated by the first hs_tracer_activate)
@@ -149,6 +151,7 @@ int hs_tracer_create(hs_tracer** out, const hs_params* params, int device_id, in
   t->W = width;
   t->H = height;
   t->cap = capacity;
+  t->tracing = hs::env::ktrace();
   const size_t c = capacity;
   const int rc = [&]() -> int {
     hs::Pool& m = t->pool;
@@ -588,8 +591,6 @@ static int act_launch(hs_tracer* t, const ActRun& r, int* n_toopt_out) {
   ma.w1 = t->w1;
   ma.h1 = t->h1;
   ma.mode = 0;
-  static const int act_dbg = getenv("HS_ACT_DBG") ? atoi(getenv("HS_ACT_DBG")) : 0;
-  ma.dbg = act_dbg;
   ma.n_tiles_x = (t->w1 - 2 + 15) / 16;
   ma.n_tiles = ma.n_tiles_x * ((t->h1 - 2 + 15) / 16);
   const int border_waves = 2 * ((t->w1 + 63) / 64) + 2 * ((t->h1 - 2 + 63) / 64);
@@ -617,10 +618,9 @@ static int act_launch(hs_tracer* t, const ActRun& r, int* n_toopt_out) {
   se.plist = t->d_act_seeds + t->cap;
   se.toopt = t->d_toopt;
   se.n_toopt = t->d_act_cnt + 1;
-  static const bool prof_on = getenv("HS_ACT_PROF") != nullptr;
   hs::Pool scratch;  // freed on every return path
   long long* d_prof = nullptr;
-  if (prof_on) HS_TRY(scratch.alloc(&d_prof, 11));
+  if (t->tracing) HS_TRY(scratch.alloc(&d_prof, 11));
   se.prof = d_prof;
   const size_t lds = se.lds_map ? map_bytes : 0;
   if (lds > 65536)

@@ -13,6 +13,7 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_track.h"
 #include "hs_ba_ctx.h"
+#include "hs_env.h"
 #include "hs_track_kernels.h"
 #include "../../include/hs_undist.h"
 #include "hs_undist_kernels.h"
@@ -50,10 +51,8 @@ struct hs_tracker : hs::Device {  // e0, e1: the per-call event pair (hs_tracker
   float* d_raw = nullptr;  // staging of a raw level-0 frame (hs_tracker_set_frame_raw)
   int pts_cap = 0;
   double* d_Tin = nullptr;
-  HsTryOut* d_out = nullptr;
   double* d_part = nullptr;       // [try_cap][2][HS_TRK_MAXG][HS_TRK_NRED] pass partials of the member workgroups
-  unsigned int* d_cnt = nullptr;  // [try_cap] timeout flags, then (cnt_bytes on) the outputs d_out: one read-back
-  HsTryOut* h_out = nullptr;      // pinned mirror: h_cnt, then h_out
+  HsTryOut* h_out = nullptr;      // the results, mapped pinned: h_cnt [try_cap] timeout flags, then (cnt_bytes on) h_out
   double* h_in = nullptr;         // pinned staging of the hypotheses (T | aff), so their upload is asynchronous
   unsigned int* h_cnt = nullptr;
   unsigned int* dh_cnt = nullptr;  // device aliases of h_cnt / h_out (mapped pinned memory)
@@ -101,17 +100,14 @@ static size_t done_bytes(int n) { return cnt_bytes(n); }  // the pinned done wor
 
 static int ensure_tries(hs_tracker* t, int n) {
   if (n <= t->try_cap) return HS_OK;
-  hs::Pool& m = t->pool;  // the pool owns d_cnt and h_cnt; d_out, h_out, h_done and the dh_* views point into them
+  hs::Pool& m = t->pool;  // the pool owns h_cnt; h_out, h_done and the dh_* views point into it
   t->try_cap = 0;
-  t->d_out = nullptr;
   t->h_out = nullptr;
   HS_TRY(m.alloc(&t->d_Tin, 9 * (size_t)n));  // T (7) | aff (2)
-  HS_TRY(m.alloc(&t->d_cnt, (cnt_bytes(n) + sizeof(HsTryOut) * n) / sizeof(unsigned int)));
-  t->d_out = reinterpret_cast<HsTryOut*>(reinterpret_cast<char*>(t->d_cnt) + cnt_bytes(n));
   HS_TRY(m.alloc(&t->d_lmlog, 3 * (size_t)HS_TRK_MAXLOG * n));
   HS_TRY(m.alloc(&t->d_lmlvl, (size_t)HS_TRK_MAXLOG * n));
   HS_TRY(m.alloc(&t->d_part, part_bytes(n) / sizeof(double)));
-  // mapped, coherent: the kernel may write the flags and records straight into it (HS_TRK_ZC, run_tries)
+  // mapped, coherent: the kernel writes the flags and records straight into it (run_tries)
   HS_TRY(m.pinned(&t->h_cnt, (cnt_bytes(n) + sizeof(HsTryOut) * n + done_bytes(n)) / sizeof(unsigned int),
                   hipHostMallocMapped | hipHostMallocCoherent));
   t->h_out = reinterpret_cast<HsTryOut*>(reinterpret_cast<char*>(t->h_cnt) + cnt_bytes(n));
@@ -153,6 +149,9 @@ static HsTrackArgs make_args(hs_tracker* t) {
 // (the rerun after a G-member meeting timed out)
 static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int single_pass, int lvl, float cutoff,
                      bool force_g1 = false) {
+  // the environment's switches (hs_env.h), read per call: the tests change them on a live tracker
+  const int env_g = hs::env::trk_g(HS_TRK_MAXG), env_gu = hs::env::trk_g_unchecked(0), env_spin = hs::env::trk_spin();
+  const bool no_evt = hs::env::trk_noevt(!t->evt), env_trace = hs::env::ktrace();
   HS_TRY(ensure_tries(t, n));
   HsTrackArgs a = make_args(t);
   a.n_inl = 0;
@@ -166,7 +165,6 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   a.coarsest = coarsest;
   a.T_in = t->d_Tin;
   a.aff_in = t->d_Tin + 7 * n;
-  a.out = t->d_out;
   a.lm_log = t->d_lmlog;
   a.lm_lvl = t->d_lmlvl;
   a.single_pass = single_pass;
@@ -179,16 +177,14 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   // per-pass meeting).  Members that are not co-resident after all (a smaller partition, kernels of other streams on
   // the CUs) make a meeting time out: the launch is then rerun with G = 1, which needs no co-residency.
   const int cap = std::max(1, t->n_cu / std::max(1, n));
-  int G = std::max(1, std::min(16, cap));
-  if (const char* e = std::getenv("HS_TRK_G")) G = std::max(1, std::min({HS_TRK_MAXG, cap, std::atoi(e)}));
-  if (const char* e = std::getenv("HS_TRK_G_UNCHECKED"))  // test hook: G without the co-residency cap
-    G = std::max(1, std::min(HS_TRK_MAXG, std::atoi(e)));
+  int G = std::max(1, std::min({HS_TRK_MAXG, cap, env_g}));
+  if (env_gu) G = std::max(1, std::min(HS_TRK_MAXG, env_gu));  // test hook: G without the co-residency cap
   if (single_pass || force_g1) G = 1;
   // a meeting's time bound: 20 ms of the device's wall clock (a healthy meeting takes a few us); after the first
   // timeout the launch's members skip every later meeting and leave the LM loop (hs_k_track, S.dead), so a launch
   // with a missing member costs ~20 ms per member before the G = 1 rerun, not 20 ms per pass
   a.spin_limit = (unsigned int)std::min<long long>(0xffffffffll, (long long)t->wclk_khz * 20);
-  if (const char* e = std::getenv("HS_TRK_SPIN")) a.spin_limit = (unsigned int)std::max(1, std::atoi(e));  // ticks (test hook)
+  if (env_spin > 0) a.spin_limit = (unsigned int)env_spin;  // ticks (test hook)
   a.G = G;
   a.nhyp = n;
   const int nblk = n * G;
@@ -196,18 +192,15 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   a.lvrec = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(t->d_part) + meet_bytes(t->try_cap));
   // levels below one workgroup's batch of points run on one member (r05_trk1 at C2: level 4's 936 points, 8 passes:
   // 0.232 -> 0.226 ms per track; a larger threshold, or fewer members at the finer levels, measured slower: the
-  // point loop outweighs the meeting there).  Env HS_TRK_GMIN, 0 = every level on all G members.
+  // point loop outweighs the meeting there)
   a.gmin = kTrkOneMemberPoints;
-  if (const char* e = std::getenv("HS_TRK_GMIN")) a.gmin = std::max(0, std::atoi(e));
-  // zero-copy results (default; env HS_TRK_ZC=0: a read-back copy behind the kernel): the lead workgroups write
-  // their records, and timed-out members their flags, into mapped pinned memory: no copy is queued behind the kernel
-  // (r04_trk5: 0.260 against 0.270 ms per track).  Polling the launch's end event instead of the blocking
-  // synchronize gained nothing measurable here and cost activation 12 % (r04_sync1), so the synchronize stays.
-  const char* zce = std::getenv("HS_TRK_ZC");
-  const bool zc = !(zce && zce[0] == '0');
-  a.cnt = zc ? t->dh_cnt : t->d_cnt;
-  a.hout = zc ? t->dh_out : nullptr;
-  a.hdone = zc ? t->dh_done : nullptr;
+  // zero-copy results: the lead workgroups write their records, and timed-out members their flags, into mapped pinned
+  // memory: no copy is queued behind the kernel (r04_trk5: 0.260 against 0.270 ms per track with a read-back copy).
+  // Polling the launch's end event instead of the blocking synchronize gained nothing measurable here and cost
+  // activation 12 % (r04_sync1), so the synchronize stays.
+  a.cnt = t->dh_cnt;
+  a.out = t->dh_out;
+  a.hdone = t->dh_done;
   a.seq = ++t->seq;
   t->last_G = G;
   // a new granule epoch per member-meeting launch; the granules and the timeout flags are zeroed only when the
@@ -215,17 +208,13 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   if (G > 1) {
     if (t->epoch == 0 || t->epoch >= (1u << (32 - HS_TRK_PASS_BITS)) - 1) {
       HS_HIP(hipMemsetAsync(t->d_part, 0, part_bytes(t->try_cap), t->stream));
-      HS_HIP(hipMemsetAsync(t->d_cnt, 0, sizeof(unsigned int) * t->try_cap, t->stream));
       std::memset(t->h_cnt, 0, sizeof(unsigned int) * t->try_cap);  // (no launch in flight: every call waits)
       t->epoch = 0;
     }
     t->epoch++;
   }
   a.epoch = t->epoch;
-  a.solve = 0;
-  if (const char* e = std::getenv("HS_TRK_SOLVE")) a.solve = std::atoi(e) == 1 ? 1 : 0;  // A/B: 1 = the LDLT
-  const char* kt = std::getenv("HS_KTRACE");
-  if (kt && kt[0] == '1' && !single_pass) {
+  if (env_trace && !single_pass) {
     const int nb = nblk;
     if (nb > t->trace_cap) {  // grown once to the largest block count (freed by hs_tracker_destroy)
       HS_TRY(t->pool.alloc(&t->d_trace, 16 * (size_t)nb));
@@ -236,20 +225,15 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
   }
   // the launch's device time (hs_tracker_last_ms) from an event pair around it, only with event timing on
   // (hs_tracker_set_event_timing; ~3-4 us of host time per call, r05_trk14): by default the host takes the results
-  // from the hypotheses' done words and last_ms stays 0.  Env HS_TRK_NOEVT=0 / 1 (read per call) forces either.
-  const char* ne = std::getenv("HS_TRK_NOEVT");
-  const bool no_evt = ne ? ne[0] == '1' : !t->evt;
+  // from the hypotheses' done words and last_ms stays 0.  HS_TRK_NOEVT=0 / 1 forces either.
   if (!no_evt) HS_HIP(hipEventRecord(t->e0, t->stream));
   hipLaunchKernelGGL(hs_k_track, dim3(nblk), dim3(512), 0, t->stream, a);
   HS_HIP(hipGetLastError());
   if (!no_evt) HS_HIP(hipEventRecord(t->e1, t->stream));
-  if (!zc)  // the timeout flags and the outputs of the n hypotheses, in one read-back
-    HS_HIP(hipMemcpyAsync(t->h_cnt, t->d_cnt, cnt_bytes(t->try_cap) + sizeof(HsTryOut) * n, hipMemcpyDeviceToHost,
-                          t->stream));
-  // zero-copy without the event pair or a trace: wait for every hypothesis' done word (its record and flags are in
-  // place before it) instead of the launch's end; bounded, then the synchronize as before.  Otherwise the synchronize.
+  // without the event pair or a trace: wait for every hypothesis' done word (its record and flags are in place
+  // before it) instead of the launch's end; bounded, then the synchronize as before.  Otherwise the synchronize.
   bool waited = false;
-  if (zc && no_evt && !a.trace) {
+  if (no_evt && !a.trace) {
     const auto t_start = std::chrono::steady_clock::now();
     for (int spins = 0;; spins++) {
       bool all = true;
@@ -261,7 +245,7 @@ static int run_tries(hs_tracker* t, int n, const double* h_in, int coarsest, int
       if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) break;
     }
   }
-  if (!waited) HS_HIP(hipStreamSynchronize(t->stream));  // (zero-copy: the records are in place once the launch completed)
+  if (!waited) HS_HIP(hipStreamSynchronize(t->stream));  // (the records are in place once the launch completed)
   for (int i = 0; G > 1 && i < n; i++)
     if (t->h_cnt[i] == t->epoch) {  // a meeting timed out: the launch's results are void, rerun every hypothesis with G = 1
       t->fallbacks++;
@@ -346,10 +330,8 @@ static int make_depth_l0(hs_tracker* t, int n_host, const int* d_n, const float*
 }
 
 // make_depth_l0 from a device count (hs_tracker_set_ref_ba) as a replayed hipGraph: the host cost of ~32 launches
-// and copies per keyframe becomes one graph launch.  HS_TRK_GRAPH=0 launches them one by one.
+// and copies per keyframe becomes one graph launch.
 static int make_depth_l0_dev(hs_tracker* t, const int* d_n, const float* pts, int stride) {
-  static const bool off = getenv("HS_TRK_GRAPH") && getenv("HS_TRK_GRAPH")[0] == '0';
-  if (off) return make_depth_l0(t, 0, d_n, pts, stride);
   auto same = [&](const DepthGraph& g) {
     if (!g.exec || g.d_n != d_n || g.pts != pts || g.stride != stride) return false;
     for (int l = 0; l < t->nlev; l++)

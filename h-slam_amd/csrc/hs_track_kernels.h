@@ -51,8 +51,7 @@ struct HsTrackArgs {
   const double* aff_in; // [n][2]
   int n_inl;            // n <= HS_TRK_INL: the hypotheses come in the arguments (inl: T [n][7] | aff [n][2])
   double inl[9 * HS_TRK_INL];
-  HsTryOut* out;        // [n]
-  HsTryOut* hout;       // [n] or null: the same records in mapped pinned host memory (written at the end)
+  HsTryOut* out;        // [n] records in mapped pinned host memory (written at the end)
   int single_pass, pass_lvl;
   float pass_cutoff;
   unsigned int spin_limit;  // polls of the G-member meeting before a hypothesis is flagged (then rerun with G = 1)
@@ -71,11 +70,10 @@ struct HsTrackArgs {
   int gmin;
   unsigned long long* lvrec;
   unsigned int epoch;
-  int solve;            // the LM step's 8x8 solve: 0 Gauss-Jordan on 64 lanes, 1 Eigen-order LDLT on 8 row lanes
   double* part;
-  unsigned int* cnt;    // [nhyp] timeout flags (a member never arrived): the epoch of the launch that timed out
-  // [nhyp] or null: the lead of hypothesis h stores seq here (system scope, release) after its record (hout) and
-  // flags, so the host may read the results without waiting for the launch's end (hs_track.cpp, run_tries)
+  unsigned int* cnt;    // [nhyp] timeout flags, mapped pinned (a member never arrived): the epoch of the launch that timed out
+  // [nhyp], mapped pinned: the lead of hypothesis h stores seq here (system scope, release) after its record (out)
+  // and flags, so the host may read the results without waiting for the launch's end (hs_track.cpp, run_tries)
   unsigned int* hdone;
   unsigned int seq;
 };

@@ -12,7 +12,7 @@
 //     hs_k_track            one workgroup (1024 threads) runs the whole coarse-to-fine LM loop of one
 //                           pose hypothesis: calcRes (Src/CoarseTracker.cpp:329-485) and the calcGSSSE
 //                           normal equations (:267-324) fused in one pass over the reference points,
-//                           block reductions, the 8x8 fp64 LDLT step (Eigen pivot order) and SE3 update.
+//                           block reductions, the 8x8 fp64 LM step (gj8_solve_wave) and SE3 update.
 //                           A grid of N workgroups runs N hypotheses of System::trackNewCoarse at once.
 // Per-point arithmetic follows the reference's fp32 operation order (fp contraction off), so the
 // in-bounds / saturation / warped-set decisions of a pass are bit-identical; the energy and Hessian
@@ -41,84 +41,6 @@ __device__ __forceinline__ double trk_readlane_f64(double v, int lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// Eigen LDLT (diagonal pivoting) solve of an 8x8 system on one wave: the pivot order is the swap sequence on the
-// original diagonal (left-looking LDLT, Eigen's ldlt_inplace::unblocked: column k is updated with the finished
-// columns j < k, temp_j = D_j L_kj, then scaled by the pivot).  Lane i (mod 8) holds row i of the pivoted matrix, so
-// column k's dot products run on the 8 row lanes at once (row k's L entries come by readlane) with the operations of
-// the single-thread form in the same order (the same result bit for bit); a single thread ran it as one ~140-
-// operation dependent fp64 chain.  One reciprocal per pivot (v_rcp_f64 + two Newton steps, within an ulp of 1 / d)
-// instead of Eigen's divisions.  A's diagonal is read scaled by dscale (the LM damping (1 + lambda)).  Every lane
-// of the wave calls it; x is uniform.
-__device__ __forceinline__ void ldlt8_solve_wave(const double* __restrict__ A, const double* __restrict__ rhs,
-                                                 double* __restrict__ x, double dscale, int lane) {
-  double dg[8];
-  int pm[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    dg[i] = fabs(A[i * 8 + i] * dscale);
-    pm[i] = i;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    double best = dg[k];
-    int bi = k;
-#pragma unroll
-    for (int j = k + 1; j < 8; j++)
-      if (dg[j] > best) { best = dg[j]; bi = j; }
-#pragma unroll
-    for (int j = k + 1; j < 8; j++)
-      if (j == bi) {
-        const double td = dg[k]; dg[k] = dg[j]; dg[j] = td;
-        const int tp = pm[k]; pm[k] = pm[j]; pm[j] = tp;
-      }
-  }
-  const int i = lane & 7;
-  int pi = pm[0];
-#pragma unroll
-  for (int q = 1; q < 8; q++) pi = i == q ? pm[q] : pi;
-  double m[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) m[j] = pm[j] == pi ? A[pi * 9] * dscale : A[pi * 8 + pm[j]];
-  double y = rhs[pi];
-  double D[8], Dinv[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    double temp[8];
-#pragma unroll
-    for (int j = 0; j < k; j++) temp[j] = D[j] * trk_readlane_f64(m[j], k);
-    double t = 0;
-#pragma unroll
-    for (int j = 0; j < k; j++) t += m[j] * temp[j];
-    if (i >= k) m[k] -= t;  // row k: the pivot's own update (the single-thread form's s)
-    const double d = trk_readlane_f64(m[k], k);
-    D[k] = d;
-    double rinv = __builtin_amdgcn_rcp(d);
-    rinv = __builtin_fma(rinv, __builtin_fma(-d, rinv, 1.0), rinv);
-    rinv = __builtin_fma(rinv, __builtin_fma(-d, rinv, 1.0), rinv);
-    Dinv[k] = fabs(d) > DBL_MIN ? rinv : 0.0;
-    if (fabs(d) > DBL_MIN && i > k) m[k] *= Dinv[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 8; k++) {  // forward: y_i -= L(i, k) y_k for k < i, in k order
-    const double yk = trk_readlane_f64(y, k);
-    if (i > k) y = y - m[k] * yk;
-  }
-  double yy[8];
-#pragma unroll
-  for (int q = 0; q < 8; q++) yy[q] = trk_readlane_f64(y, q) * Dinv[q];
-#pragma unroll
-  for (int q = 7; q >= 0; q--)
-#pragma unroll
-    for (int j = q + 1; j < 8; j++) yy[q] = yy[q] - trk_readlane_f64(m[q], j) * yy[j];
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    double v = yy[0];
-#pragma unroll
-    for (int r = 1; r < 8; r++) v = pm[r] == q ? yy[r] : v;
-    x[q] = pm[0] == q ? yy[0] : v;
-  }
-}
-
 __device__ __forceinline__ double trk_bperm_f64(double v, int src_lane) {
   const long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, (int)(b & 0xffffffffll));
@@ -126,15 +48,16 @@ __device__ __forceinline__ double trk_bperm_f64(double v, int src_lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-// The same damped 8x8 solve by Gauss-Jordan elimination on the whole wave: lane 8 i + j holds A(i, j) (the diagonal
-// scaled by dscale) and rhs(i).  Per pivot k every lane fetches A(k, j) and A(i, k) by ds_bpermute and A(k, k),
-// rhs(k) by readlane; row k is scaled by 1 / A(k, k) and every other row loses A(i, k) / A(k, k) times row k.  After
-// eight pivots rhs holds x.  The system is the LM-damped H + lambda diag(H) (symmetric positive semi-definite), so
-// elimination in the natural order is stable without Eigen's diagonal pivoting; an exactly zero pivot (a zero row
-// and column: an affine parameter held fixed) gives x_k = 0 as Eigen's LDLT solve does.  Depth: 8 x (one LDS
-// exchange, a reciprocal, an fma) against the LDLT's 8 dependent dot products plus two substitutions; the result
-// differs from the LDLT's by rounding only (tests/test_gpu_track.py: the LM logs and poses within the oracle's own
-// summation-order spread).  Every lane of the wave calls it; x is uniform.
+// The LM step's damped 8x8 solve by Gauss-Jordan elimination on the whole wave: lane 8 i + j holds A(i, j) (A's
+// diagonal read scaled by dscale, the LM damping (1 + lambda)) and rhs(i).  Per pivot k every lane fetches A(k, j)
+// and A(i, k) by ds_bpermute and A(k, k), rhs(k) by readlane; row k is scaled by 1 / A(k, k) (v_rcp_f64 + two Newton
+// steps, within an ulp of 1 / d) and every other row loses A(i, k) / A(k, k) times row k.  After eight pivots rhs
+// holds x.  The system is the LM-damped H + lambda diag(H) (symmetric positive semi-definite), so elimination in the
+// natural order is stable without Eigen's diagonal pivoting; an exactly zero pivot (a zero row and column: an affine
+// parameter held fixed) gives x_k = 0 as Eigen's LDLT solve does.  Depth: 8 x (one LDS exchange, a reciprocal, an
+// fma) against an LDLT's 8 dependent dot products plus two substitutions; the result differs from the reference's
+// LDLT by rounding only (tests/test_gpu_track.py: the LM logs and poses within the oracle's own summation-order
+// spread).  Every lane of the wave calls it; x is uniform.
 __device__ __forceinline__ void gj8_solve_wave(const double* __restrict__ A, const double* __restrict__ rhs,
                                                double* __restrict__ x, double dscale, int lane) {
   const int i = lane >> 3, j = lane & 7;
@@ -600,23 +523,18 @@ __device__ void trk_setup(const HsTrackArgs& a, TrkShared& S, const double T7[7]
   trk_setup_part(a, S, T7, aff, lvl, cutoff, false);
 }
 
-// the lead's output record, LDS -> a.out[h] (device) and, when the caller asked for it, a.hout[h] (mapped pinned
-// host memory: the host reads it once the launch has completed, with no copy behind the kernel); wave 0, 8 B a lane
+// the lead's output record, LDS -> a.out[h] (mapped pinned host memory: the host reads it once the done word or the
+// launch's end says so, with no copy behind the kernel); wave 0, 8 B a lane
 __device__ void trk_publish(const HsTrackArgs& a, TrkShared& S, int h, bool lead) {
   __syncthreads();
   if (!lead || threadIdx.x >= 64) return;
   constexpr int NW = sizeof(HsTryOut) / 8;
   static_assert(sizeof(HsTryOut) % 8 == 0, "output record in 8-B words");
   const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&S.out);
-  unsigned long long* dd = reinterpret_cast<unsigned long long*>(a.out + h);
-  unsigned long long* dh = a.hout ? reinterpret_cast<unsigned long long*>(a.hout + h) : nullptr;
-  for (int k = threadIdx.x; k < NW; k += 64) {
-    const unsigned long long w = src[k];
-    dd[k] = w;
-    if (dh) dh[k] = w;
-  }
+  unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.out + h);
+  for (int k = threadIdx.x; k < NW; k += 64) dst[k] = src[k];
   // the record (and any timeout flag this wave stored) before the done word: the release orders the wave's stores
-  if (a.hdone && threadIdx.x == 0) __hip_atomic_store(a.hdone + h, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 0) __hip_atomic_store(a.hdone + h, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace
@@ -782,10 +700,9 @@ __global__ __launch_bounds__(TRK_NT) void hs_k_track(HsTrackArgs a) {
         double mb[8], inc[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) mb[i] = -S.bs[i];
-        if (a.solve == 0)
-          gj8_solve_wave(S.Hs, mb, inc, 1 + S.lambda, tid & 63);
-        else
-          ldlt8_solve_wave(S.Hs, mb, inc, 1 + S.lambda, tid & 63);
+        // (the lane index read here, as in trk_level_meet: with tid & 63 the solve's lane terms are formed at the
+        // kernel's entry and kept live across the point loop, which spills 7 VGPRs instead of 1)
+        gj8_solve_wave(S.Hs, mb, inc, 1 + S.lambda, __lane_id());
         if ((tid & 63) == 0) {
           const long long lm1 = a.trace ? clock64() + (long long)(inc[7] * 0.0) : 0;
           float extrapFac = 1;

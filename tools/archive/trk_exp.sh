@@ -1,5 +1,5 @@
-# tracker A/B over HS_TRK_GMIN (levels below it run on one member).  usage: tools/trk_exp.sh TAG [values...]
-cd $GRAFT_REPO_ROOT && O=gpurun_out/${1:-trk} && mkdir -p $O; shift
+# tracker A/B over HS_TRK_GMIN (levels below it run on one member).  usage: tools/archive/trk_exp.sh TAG [values...]  (archived: the switch was removed with its A/B path)
+cd "$(dirname "$0")/../.." && O=out/${1:-trk} && mkdir -p $O; shift
 for V in ${@:-0 4096}; do
   HS_TRK_GMIN=$V timeout -k 10 120 python bench.py --full --workload track --steps 50 --warmup 5 --no-cpu > $O/track_$V.json 2>$O/track_$V.err || { echo "track $V failed"; tail -5 $O/track_$V.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/track_$V.json'));print('gmin $V', round(d['ms_per_step'],4), 'ms  device', round(d['config']['device_ms_per_track'],4), 'passes', d['config']['passes'])"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-kernel rocprofv3 stats (kernel trace only, no counters) + the bench line for a few runs.
 # usage: tools/kstats.sh TAG "NAME|ENV ASSIGNMENTS|bench args" ...
-#   e.g. tools/kstats.sh r06_k1 "p200k|HS_TH_BESIDE=0|--full --points 200000 --steps 20 --warmup 3 --no-cpu"   (--full: the per-phase split is printed)
+#   e.g. tools/kstats.sh r06_k1 "p200k|HS_LIN8_HIST=0|--full --points 200000 --steps 20 --warmup 3 --no-cpu"   (--full: the per-phase split is printed)
 # Outputs gpurun_out/TAG/NAME/{bench.json,bench.err,prof/...kernel_stats.csv}; prints value, step and the top kernels.
 TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
