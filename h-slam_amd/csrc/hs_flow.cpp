@@ -48,6 +48,8 @@ struct hs_flow : hs::Device {
   float* d_cerr = nullptr;
   hs_flow_counts* d_counts = nullptr;
   hs_flow_counts* h_counts = nullptr;  // pinned
+  float* d_mean = nullptr;             // hs_flow_mean_flow_device's result
+  float* h_mean = nullptr;             // pinned
   int n = 0;
   bool have_first = false, tracked = false;
   long long first_id = 0;  // counts the first frames set
@@ -278,6 +280,8 @@ int hs_flow_create(hs_flow** out, int device_id, int width, int height, int capa
     HS_TRY(m.alloc(&f->d_cerr, c));
     HS_TRY(m.alloc(&f->d_counts, 1));
     HS_TRY(m.pinned(&f->h_counts, 1));
+    HS_TRY(m.alloc(&f->d_mean, 1));
+    HS_TRY(m.pinned(&f->h_mean, 1));
     HS_HIP(hipStreamSynchronize(f->stream));
     return HS_OK;
   }();
@@ -372,6 +376,21 @@ int hs_flow_track_image(hs_flow* f, hs_image* im, float max_l1_error, int* n_goo
   return run_track(f, f->d_raw, max_l1_error, n_good);
 }
 
+// Initialize()'s first-frame branch with cvImgL copied device to device from a device image and the keys from the host.
+int hs_flow_set_first_image(hs_flow* f, hs_image* im, int n, const float* xy) {
+  if (!f || !im || (n > 0 && !xy)) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (n < 0 || n > f->cap)
+    return hs::fail(HS_ERR_INVALID, std::to_string(n) + " points, capacity is " + std::to_string(f->cap));
+  HsImageView v;
+  HS_TRY(hs_image_view(im, f->device, f->W, f->H, 1, true, &v));
+  HS_HIP(hipSetDevice(f->device));
+  HS_HIP(hipStreamWaitEvent(f->stream, v.ready, 0));
+  HS_HIP(hipMemcpyAsync(f->d_raw, v.img8, (size_t)f->W * f->H, hipMemcpyDeviceToDevice, f->stream));
+  HS_HIP(hs_image_consumed(im, f->stream));
+  if (n) HS_HIP(hipMemcpyAsync(f->d_first, xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, f->stream));
+  return finish_first(f, f->d_raw, n);
+}
+
 int hs_flow_get(hs_flow* f, int* n, float* first_xy, float* prev_xy, float* xy, uint8_t* status, float* err,
                 uint8_t* good) {
   if (!f) return hs::fail(HS_ERR_INVALID, "null flow");
@@ -407,6 +426,24 @@ int hs_flow_mean_flow(hs_flow* f, float* mean) {
     count++;
   }
   *mean = (float)acc / (float)count;
+  return HS_OK;
+}
+
+int hs_flow_mean_flow_device(hs_flow* f, float* mean) {
+  if (!f || !mean) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (!f->tracked) return hs::fail(HS_ERR_STATE, "no track yet: there is no flow to average");
+  HS_HIP(hipSetDevice(f->device));
+  HsFlowMeanArgs a;
+  a.n = f->n;
+  a.prev_xy = f->d_pts[f->pcur ^ 1];
+  a.xy = f->d_pts[f->pcur];
+  a.good = f->d_good;
+  a.mean = f->d_mean;
+  hipLaunchKernelGGL(hs_k_flow_mean, dim3(1), dim3(256), 0, f->stream, a);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(f->h_mean, f->d_mean, sizeof(float), hipMemcpyDeviceToHost, f->stream));
+  HS_HIP(hipStreamSynchronize(f->stream));
+  *mean = *f->h_mean;
   return HS_OK;
 }
 

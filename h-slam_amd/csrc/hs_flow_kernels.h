@@ -62,6 +62,15 @@ __global__ void hs_k_flow_pyrdown(HsFlowDownArgs a);
 __global__ void hs_k_flow_scharr(HsFlowScharrArgs a);
 __global__ void hs_k_flow_lk(HsFlowLkArgs a);
 
+// ComputeMeanOpticalFlow(MatchedPtsBkp, MatchedPts) over the good points
+struct HsFlowMeanArgs {
+  int n;
+  const float2 *prev_xy, *xy;
+  const uint8_t* good;
+  float* mean;  // one float
+};
+__global__ void hs_k_flow_mean(HsFlowMeanArgs a);  // 1 block of 256
+
 // FirstFramePts (= mvKeys[i].pt, n pairs) where the last hs_flow_set_first* left them on the device; false before
 // the first one.  Every hs_flow entry waits for its own work before it returns, so the pairs are complete; only the
 // next hs_flow_set_first* rewrites them, so a consumer waits for its own reads before it returns

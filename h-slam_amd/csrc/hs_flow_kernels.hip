@@ -279,3 +279,46 @@ __global__ __launch_bounds__(256) void hs_k_flow_lk(HsFlowLkArgs a) {
     if (iters) atomicAdd(a.n_iters, (unsigned long long)iters);
   }
 }
+
+// hs_flow_mean_flow on the device, bit for bit.  The norms of a chunk of keys are made in parallel into LDS; the
+// reference's accumulate into an int, acc = (int)((float)acc + norm), rounds the float sum before it truncates, so it
+// is not associative and stays one ordered chain: lane 0 walks the chunk in key order.  A key that is not good is stored
+// as -1 (a norm is never negative) and leaves acc alone through a select, not a branch, so the chain's LDS reads (four
+// keys each) do not wait for the chain.
+__global__ __launch_bounds__(256) void hs_k_flow_mean(HsFlowMeanArgs a) {
+  constexpr int kChunk = 1024;
+  __shared__ float4 norm4[kChunk / 4];
+  float* norm = reinterpret_cast<float*>(norm4);
+  const int t = threadIdx.x;
+  int acc = 0, count = 0;
+  for (int c0 = 0; c0 < a.n; c0 += kChunk) {
+    for (int k = t; k < kChunk; k += 256) {
+      const int i = c0 + k;
+      float v = -1.f;
+      if (i < a.n && a.good[i]) {
+        const float2 p = a.prev_xy[i], q = a.xy[i];
+        const float dx = p.x - q.x, dy = p.y - q.y;
+        v = (float)sqrt((double)dx * dx + (double)dy * dy);
+      }
+      norm[k] = v;
+    }
+    __syncthreads();
+    if (t == 0) {
+      const int len4 = ((a.n - c0 < kChunk ? a.n - c0 : kChunk) + 3) / 4;
+#pragma unroll 4
+      for (int k = 0; k < len4; k++) {
+        const float4 v = norm4[k];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int next = (int)((float)acc + e[j]);
+          const bool g = !(e[j] < 0.f);
+          acc = g ? next : acc;
+          count += g ? 1 : 0;
+        }
+      }
+    }
+    __syncthreads();  // the next chunk rewrites the LDS
+  }
+  if (t == 0) *a.mean = (float)acc / (float)count;  // 0 / 0: NaN with no good key
+}

@@ -37,6 +37,15 @@ struct hs_twoview : hs::Device {
   float *d_z = nullptr, *d_p3d = nullptr;
   hipEvent_t ev_flow = nullptr;           // orders a fit behind the flow's last track
   hipEvent_t ev_k[kTvStages + 1] = {};    // between the kernels of a fit
+  hipEvent_t ev_d[3] = {};                // around the two kernels of a draw
+  // the draw of the sets: the generator's state (randomGen) is the host's, its words go up, m comes back
+  uint64_t rng = 0;
+  int* d_all = nullptr;
+  uint32_t* d_words = nullptr;
+  uint32_t* h_words = nullptr;  // pinned
+  int* h_draw = nullptr;        // pinned: hs_twoview_draw's sets and m
+  int n_sets_fit = 0;           // the sets of the last fit at d_sets
+  bool drew = false;
   int n = 0, ns_h = 0, ns_f = 0, n_rt = 0;
   bool have_keys = false, have_fit = false, fit_ok = false, timed = false;
   hs_flow* fit_flow = nullptr;            // the flow of the last fit (null: host-fed), identified by
@@ -78,6 +87,9 @@ HsTvArgs args_of(hs_twoview* tv, int n, int ns_h, int ns_f) {
   a.tri = tv->d_tri;
   a.z = tv->d_z;
   a.p3d = tv->d_p3d;
+  a.all = tv->d_all;
+  a.words = tv->d_words;
+  a.draw_out = tv->d_sets;
   return a;
 }
 
@@ -102,6 +114,33 @@ int check_sets(int n, int n_sets, const int32_t* sets, const uint8_t* status) {
   return HS_OK;
 }
 
+// cv::RNG (the contract of include/hs_twoview.h)
+inline uint64_t rng_seeded(uint64_t seed) { return seed ? seed : 0xffffffffull; }
+inline uint32_t rng_next(uint64_t* state) {
+  *state = (uint64_t)(uint32_t)*state * 4164903690u + (uint32_t)(*state >> 32);
+  return (uint32_t)*state;
+}
+
+int check_n_sets(int n_sets) {
+  if (n_sets < 1 || n_sets > kTvMaxSets)
+    return hs::fail(HS_ERR_INVALID, "n_sets is " + std::to_string(n_sets) + ", must be 1 .. 256");
+  return HS_OK;
+}
+
+// The words of a draw of n_sets sets from tv's state, uploaded on the stream; after[0] / after[1] = the state behind
+// 7 / 8 words per set (m == 8 takes 7).  The context's state is not moved.
+int upload_words(hs_twoview* tv, int n_sets, uint64_t after[2]) {
+  uint64_t st = tv->rng;
+  for (int i = 0; i < 8 * n_sets; i++) {
+    if (i == 7 * n_sets) after[0] = st;
+    tv->h_words[i] = rng_next(&st);
+  }
+  after[1] = st;
+  HS_HIP(hipMemcpyAsync(tv->d_words, tv->h_words, sizeof(uint32_t) * 8 * (size_t)n_sets, hipMemcpyHostToDevice,
+                        tv->stream));
+  return HS_OK;
+}
+
 #define HS_TV_LAUNCH(kernel, grid, block, stage)                      \
   do {                                                                \
     hipLaunchKernelGGL(kernel, grid, dim3(block), 0, s, a);           \
@@ -110,10 +149,19 @@ int check_sets(int n, int n_sets, const int32_t* sets, const uint8_t* status) {
   } while (0)
 
 // the launches of one fit behind its inputs; `a` names where the inputs are
-int run_fit(hs_twoview* tv, HsTvArgs a, hs_flow* flow, long long first_id, hs_twoview_result* result) {
+// (a.n_draw != 0: the sets are drawn first, from the words upload_words left, and `after` holds the two candidate states)
+int run_fit(hs_twoview* tv, HsTvArgs a, hs_flow* flow, long long first_id, hs_twoview_result* result,
+            const uint64_t* after = nullptr) {
   hipStream_t s = tv->stream;
   const int n = a.n, ns = a.ns_h;
   HS_TV_LAUNCH(hs_k_tv_begin, dim3(1), 256, -1);
+  if (a.n_draw) {
+    HS_HIP(hipEventRecord(tv->ev_d[0], s));
+    HS_TV_LAUNCH(hs_k_tv_good_list, dim3(1), 1024, -1);
+    HS_HIP(hipEventRecord(tv->ev_d[1], s));
+    HS_TV_LAUNCH(hs_k_tv_draw, dim3((a.n_draw + 63) / 64), 64, -1);
+    HS_HIP(hipEventRecord(tv->ev_d[2], s));
+  }
   HS_TV_LAUNCH(hs_k_tv_pack, dim3(blocks((size_t)(n > ns * 8 ? n : ns * 8))), 256, -1);
   HS_HIP(hipEventRecord(tv->ev_k[0], s));
   HS_TV_LAUNCH(hs_k_tv_normalize, dim3(2), 256, 0);
@@ -127,7 +175,28 @@ int run_fit(hs_twoview* tv, HsTvArgs a, hs_flow* flow, long long first_id, hs_tw
   // the one read-back: the result record (with the status rule's verdict)
   HS_HIP(hipMemcpyAsync(tv->h_st, tv->d_st, sizeof(HsTvState), hipMemcpyDeviceToHost, s));
   HS_HIP(hipStreamSynchronize(s));
+  if (a.n_draw) tv->drew = true;
+  if (tv->h_st->bad == 2) {
+    // fewer than 8 matched keys: no kernel of the fit ran, the state does not move
+    hs_twoview_result r;
+    std::memset(&r, 0, sizeof r);
+    r.why = 5;
+    r.model = r.best_h = r.best_f = r.best_rt = -1;
+    r.reserved[0] = (int32_t)(uint32_t)tv->rng;
+    r.reserved[1] = (int32_t)(uint32_t)(tv->rng >> 32);
+    tv->have_fit = tv->timed = true;
+    tv->fit_ok = false;
+    tv->last = r;
+    if (result) *result = r;
+    return HS_OK;
+  }
   if (tv->h_st->bad) return hs::fail(HS_ERR_INVALID, "a set points at a key with status 0");
+  if (a.n_draw) {
+    tv->rng = after[tv->h_st->m == 8 ? 0 : 1];
+    tv->h_st->res.reserved[0] = (int32_t)(uint32_t)tv->rng;
+    tv->h_st->res.reserved[1] = (int32_t)(uint32_t)(tv->rng >> 32);
+  }
+  tv->n_sets_fit = ns;
   tv->n = n;
   tv->ns_h = tv->ns_f = ns;
   tv->n_rt = tv->h_st->n_rt;
@@ -177,6 +246,7 @@ int hs_twoview_create(hs_twoview** out, int device_id, int capacity, const doubl
     hipStream_t s = tv->stream;
     HS_HIP(hipEventCreateWithFlags(&tv->ev_flow, hipEventDisableTiming));
     for (hipEvent_t& e : tv->ev_k) HS_HIP(hipEventCreate(&e));
+    for (hipEvent_t& e : tv->ev_d) HS_HIP(hipEventCreate(&e));
     HS_TRY(m.alloc_zero(&tv->d_st, 1, s));
     HS_TRY(m.pinned(&tv->h_st, 1));
     HS_TRY(m.pinned(&tv->h_sets, (size_t)kTvMaxSets * 8));
@@ -200,6 +270,11 @@ int hs_twoview_create(hs_twoview** out, int device_id, int capacity, const doubl
     HS_TRY(m.alloc_zero(&tv->d_tri, c, s));
     HS_TRY(m.alloc_zero(&tv->d_z, c, s));
     HS_TRY(m.alloc_zero(&tv->d_p3d, 3 * c, s));
+    HS_TRY(m.alloc_zero(&tv->d_all, c, s));
+    HS_TRY(m.alloc_zero(&tv->d_words, (size_t)kTvMaxSets * 8, s));
+    HS_TRY(m.pinned(&tv->h_words, (size_t)kTvMaxSets * 8));
+    HS_TRY(m.pinned(&tv->h_draw, (size_t)kTvMaxSets * 8 + 1));
+    tv->rng = rng_seeded(0);
     HS_HIP(hipStreamSynchronize(s));
     return HS_OK;
   }();
@@ -215,6 +290,8 @@ void hs_twoview_destroy(hs_twoview* tv) {
   tv->pool.release_all();
   if (tv->ev_flow) (void)hipEventDestroy(tv->ev_flow);
   for (hipEvent_t e : tv->ev_k)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : tv->ev_d)
     if (e) (void)hipEventDestroy(e);
   tv->close();
   delete tv;
@@ -261,6 +338,105 @@ int hs_twoview_fit_flow(hs_twoview* tv, hs_flow* flow, int n_sets, const int32_t
   a.in2 = k.matched;
   a.in_status = k.good;
   return run_fit(tv, a, flow, k.first_id, result);  // waits: the flow's arrays are free again on return
+}
+
+int hs_twoview_rng_seed(hs_twoview* tv, uint64_t seed) {
+  if (!tv) return hs::fail(HS_ERR_INVALID, "null two-view fit");
+  tv->rng = rng_seeded(seed);
+  return HS_OK;
+}
+
+int hs_twoview_rng_skip(hs_twoview* tv, uint64_t n_next) {
+  if (!tv) return hs::fail(HS_ERR_INVALID, "null two-view fit");
+  if (n_next > (1ull << 30)) return hs::fail(HS_ERR_INVALID, "n_next above 2^30: a skip is a host loop");
+  for (uint64_t i = 0; i < n_next; i++) rng_next(&tv->rng);
+  return HS_OK;
+}
+
+int hs_twoview_rng_state(hs_twoview* tv, uint64_t* state) {
+  if (!tv || !state) return hs::fail(HS_ERR_INVALID, "null argument");
+  *state = tv->rng;
+  return HS_OK;
+}
+
+int hs_twoview_draw(hs_twoview* tv, int n, const uint8_t* status, int n_sets, int32_t* sets_out, int* m_out) {
+  if (!tv || !status || !sets_out) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (n < 8 || n > tv->cap)
+    return hs::fail(HS_ERR_INVALID, std::to_string(n) + " keys, must be 8 .. the capacity " + std::to_string(tv->cap));
+  HS_TRY(check_n_sets(n_sets));
+  int good = 0;
+  for (int i = 0; i < n; i++) good += status[i] != 0;
+  if (good < 8)
+    return hs::fail(HS_ERR_INVALID, std::to_string(good) + " keys with status != 0: a set takes 8");
+  HS_HIP(hipSetDevice(tv->device));
+  hipStream_t s = tv->stream;
+  uint64_t after[2];
+  HS_TRY(upload_words(tv, n_sets, after));
+  HS_HIP(hipMemcpyAsync(tv->d_in_status, status, (size_t)n, hipMemcpyHostToDevice, s));
+  // the fit's own sets stay where hs_twoview_get_sets reads them: the draw lands in the host-fed fit's input buffer
+  HsTvArgs a = args_of(tv, n, 0, 0);
+  a.n_draw = n_sets;
+  a.draw_out = tv->d_in_sets;
+  HS_HIP(hipEventRecord(tv->ev_d[0], s));
+  HS_TV_LAUNCH(hs_k_tv_good_list, dim3(1), 1024, -1);
+  HS_HIP(hipEventRecord(tv->ev_d[1], s));
+  HS_TV_LAUNCH(hs_k_tv_draw, dim3((n_sets + 63) / 64), 64, -1);
+  HS_HIP(hipEventRecord(tv->ev_d[2], s));
+  const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+  HS_HIP(hipMemcpyAsync(tv->h_draw, tv->d_in_sets, sizeof(int) * 8 * (size_t)n_sets, d2h, s));
+  HS_HIP(hipMemcpyAsync(tv->h_draw + 8 * (size_t)n_sets, &tv->d_st->m, sizeof(int), d2h, s));
+  HS_HIP(hipStreamSynchronize(s));
+  const int m = tv->h_draw[8 * (size_t)n_sets];
+  std::memcpy(sets_out, tv->h_draw, sizeof(int) * 8 * (size_t)n_sets);
+  if (m_out) *m_out = m;
+  tv->rng = after[m == 8 ? 0 : 1];
+  tv->drew = true;
+  return HS_OK;
+}
+
+int hs_twoview_fit_flow_drawn(hs_twoview* tv, hs_flow* flow, int n_sets, hs_twoview_result* result) {
+  if (!tv || !flow) return hs::fail(HS_ERR_INVALID, "null argument");
+  HsFlowKeys k;
+  if (!hs_flow_tracked_keys(flow, &k) || !k.tracked)
+    return hs::fail(HS_ERR_STATE, "the flow has not tracked a frame yet (hs_flow_set_first, hs_flow_track)");
+  if (k.device != tv->device) return hs::fail(HS_ERR_INVALID, "flow and two-view fit are on different devices");
+  if (k.n < 8 || k.n > tv->cap)
+    return hs::fail(HS_ERR_INVALID, "the flow holds " + std::to_string(k.n) + " keys, must be 8 .. the capacity " +
+                                        std::to_string(tv->cap));
+  HS_TRY(check_n_sets(n_sets));
+  HS_HIP(hipSetDevice(tv->device));
+  hipStream_t s = tv->stream;
+  uint64_t after[2];
+  HS_TRY(upload_words(tv, n_sets, after));
+  HS_HIP(hipEventRecord(tv->ev_flow, k.stream));
+  HS_HIP(hipStreamWaitEvent(s, tv->ev_flow, 0));
+  HsTvArgs a = args_of(tv, k.n, n_sets, n_sets);
+  a.n_draw = n_sets;
+  a.in1 = k.first;
+  a.in2 = k.matched;
+  a.in_status = k.good;
+  return run_fit(tv, a, flow, k.first_id, result, after);  // waits: the flow's arrays are free again on return
+}
+
+int hs_twoview_get_sets(hs_twoview* tv, int32_t* sets) {
+  if (!tv || !sets) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(need_keys(tv));
+  HS_HIP(hipSetDevice(tv->device));
+  HS_HIP(hipMemcpyAsync(sets, tv->d_sets, sizeof(int) * 8 * (size_t)tv->n_sets_fit, hipMemcpyDeviceToHost, tv->stream));
+  HS_HIP(hipStreamSynchronize(tv->stream));
+  return HS_OK;
+}
+
+int hs_twoview_last_draw_stats(hs_twoview* tv, double* ms) {
+  if (!tv || !ms) return hs::fail(HS_ERR_INVALID, "null argument");
+  if (!tv->drew) return hs::fail(HS_ERR_STATE, "no draw yet");
+  HS_HIP(hipSetDevice(tv->device));
+  for (int k = 0; k < 2; k++) {
+    float t = 0;
+    HS_HIP(hipEventElapsedTime(&t, tv->ev_d[k], tv->ev_d[k + 1]));
+    ms[k] = t;
+  }
+  return HS_OK;
 }
 
 int hs_twoview_get(hs_twoview* tv, uint8_t* inliers_h, uint8_t* inliers_f, float* scores_h, float* scores_f,

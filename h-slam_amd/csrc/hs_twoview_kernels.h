@@ -11,7 +11,9 @@ constexpr int kTvMaxRt = 8;
 
 // what the launches of one fit hand to each other, and the record the host reads back
 struct HsTvState {
-  int bad;                 // a set points at a key with status 0: every later kernel of the fit returns at once
+  int bad;                 // 1: a set points at a key with status 0; 2: fewer than 8 matched keys to draw from.  Every
+                           // later kernel of the fit returns at once
+  int m;                   // hs_k_tv_good_list: the keys with status != 0
   int best_h, best_f;      // the winners (-1: no score above 0)
   float SH, SF;
   int n_in_h, n_in_f;      // the winners' inliers (integer atomics)
@@ -48,9 +50,16 @@ struct HsTvArgs {
   uint8_t* tri;     // [n]
   float* z;         // [n]
   float* p3d;       // [n][3]
+  // the draw of the sets (hs_k_tv_good_list, hs_k_tv_draw)
+  int n_draw;            // the sets to draw (0: the sets are the caller's)
+  int* all;              // [n]: the keys with in_status != 0, ascending
+  const uint32_t* words; // [8 * n_draw]: the generator's next() values in order
+  int* draw_out;         // [n_draw][8]
 };
 
 __global__ void hs_k_tv_begin(HsTvArgs a);      // 1 block: the status rule of the sets, the counters' reset
+__global__ void hs_k_tv_good_list(HsTvArgs a);  // 1 block of 1024: the stable compaction of in_status != 0, and m
+__global__ void hs_k_tv_draw(HsTvArgs a);       // one lane per set: the swap-and-pop over `all`
 __global__ void hs_k_tv_pack(HsTvArgs a);       // n threads: keys, status, sets into the state
 __global__ void hs_k_tv_normalize(HsTvArgs a);  // 2 blocks: one per image
 __global__ void hs_k_tv_hypotheses(HsTvArgs a); // one wave per (set, model): ns_h + ns_f blocks of 64

@@ -217,6 +217,62 @@ __global__ __launch_bounds__(256) void hs_k_tv_begin(HsTvArgs a) {
   }
 }
 
+// The ascending list of the keys with in_status != 0 (a stable compaction) and its length m.  One block walks the keys
+// in chunks of its own size behind a running base, so any n fits one launch: within a chunk a wave's ballot ranks its
+// lanes, and the waves' counts in LDS place the wave.  Integer counts only.
+__global__ __launch_bounds__(1024) void hs_k_tv_good_list(HsTvArgs a) {
+  constexpr int kNt = 1024, kWaves = kNt / 64;
+  __shared__ int wcnt[kWaves];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  int base = 0;
+  for (int c0 = 0; c0 < a.n; c0 += kNt) {
+    const int i = c0 + t;
+    const bool f = i < a.n && a.in_status[i] != 0;
+    const unsigned long long mask = __ballot(f);
+    if (lane == 0) wcnt[w] = __popcll(mask);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int k = 0; k < kWaves; k++) {
+      const int c = wcnt[k];
+      if (k < w) off += c;
+      tot += c;
+    }
+    if (f) a.all[base + off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
+    base += tot;
+    __syncthreads();  // wcnt is rewritten by the next chunk
+  }
+  if (t == 0) {
+    a.st->m = base;
+    if (base < 8) a.st->bad = 2;
+  }
+}
+
+// mvSets (Initializer.cpp:404-432), one lane per set: r = uniform(0, size - 1) from the set's words, sets[it][j] =
+// avail[r], avail[r] = avail[size - 1], pop.  avail is never copied: the swap-and-pop rewrites at most eight slots, which
+// the lane keeps in registers (the latest override of a slot wins); every other slot is read from `all`.  With m == 8
+// the eighth draw is uniform(0, 0) and takes no word, so a set's words are 7 apart.
+__global__ __launch_bounds__(64) void hs_k_tv_draw(HsTvArgs a) {
+  const int it = blockIdx.x * 64 + threadIdx.x;
+  const int m = a.st->m;
+  if (it >= a.n_draw || m < 8) return;
+  const uint32_t* w = a.words + (size_t)it * (m == 8 ? 7 : 8);
+  int slot[8], val[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int last = m - j - 1;
+    const int r = last > 0 ? (int)(w[j] % (unsigned)last) : 0;
+    int vr = a.all[r], vl = a.all[last];
+#pragma unroll
+    for (int k = 0; k < j; k++) {
+      if (slot[k] == r) vr = val[k];
+      if (slot[k] == last) vl = val[k];
+    }
+    a.draw_out[it * 8 + j] = vr;
+    slot[j] = r;
+    val[j] = vl;
+  }
+}
+
 __global__ __launch_bounds__(256) void hs_k_tv_pack(HsTvArgs a) {
   if (a.st->bad) return;
   const int i = blockIdx.x * kBlock + threadIdx.x;

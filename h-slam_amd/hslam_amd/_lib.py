@@ -237,6 +237,7 @@ SIGNATURES = {
     "hs_flow_track_u8": ([VP, VP, VP, C.c_float, VP], I),
     "hs_flow_get": ([VP] * 8, I),
     "hs_flow_mean_flow": ([VP, VP], I),
+    "hs_flow_mean_flow_device": ([VP, VP], I),
     "hs_flow_calc": ([VP, VP, VP, I, VP, VP, VP, VP, VP], I),
     "hs_flow_get_pyramid": ([VP, I, I, VP, VP, VP, VP], I),
     "hs_flow_last_stats": ([VP, VP, VP, VP], I),
@@ -253,6 +254,7 @@ SIGNATURES = {
     "hs_selector_make_maps_image": ([VP, I, VP, C.c_float, I, C.c_float, VP, VP], I),
     "hs_extractor_extract_image": ([VP, VP, VP, VP], I),
     "hs_flow_track_image": ([VP, VP, C.c_float, VP], I),
+    "hs_flow_set_first_image": ([VP, VP, I, VP], I),
     "hs_image_to_ba": ([VP, VP, I], I),
     # include/hs_init.h
     "hs_refiner_set_first_image": ([VP, VP, C.c_float], I),
@@ -272,6 +274,13 @@ SIGNATURES = {
     "hs_twoview_last_stats": ([VP, VP], I),
     "hs_twoview_score_models": ([VP, I, VP, VP, I, VP], I),
     "hs_twoview_check_rt": ([VP, I, VP, VP, VP], I),
+    "hs_twoview_rng_seed": ([VP, C.c_uint64], I),
+    "hs_twoview_rng_skip": ([VP, C.c_uint64], I),
+    "hs_twoview_rng_state": ([VP, VP], I),
+    "hs_twoview_draw": ([VP, I, VP, I, VP, VP], I),
+    "hs_twoview_fit_flow_drawn": ([VP, VP, I, VP], I),
+    "hs_twoview_get_sets": ([VP, VP], I),
+    "hs_twoview_last_draw_stats": ([VP, VP], I),
     # include/hs_map.h
     "hs_map_create": ([VP, I, I], I),
     "hs_map_destroy": ([VP], None),

@@ -10,7 +10,8 @@ later frame, with the reference's bookkeeping of previous points, outputs and go
     n_good = fl.track_u8(undistorter, raw, 7)    # cvImgL made from the camera's raw frame on the device
     n_good = fl.track_image(image, 7)            # cvImgL of a DeviceImage (hslam_amd.image), on the device
     r = fl.get()                                 # dict(first_xy, prev_xy, xy, status, err, good)
-    m = fl.mean_flow()                           # ComputeMeanOpticalFlow(MatchedPtsBkp, MatchedPts)
+    m = fl.mean_flow()                           # ComputeMeanOpticalFlow(MatchedPtsBkp, MatchedPts), on the host
+    m = fl.mean_flow_device()                    # the same 4 bytes made on the device
     r = fl.calc(prev8, next8, prev_xy[, init_xy])  # one stand-alone calcOpticalFlowPyrLK: dict(xy, status, err)
 """
 from __future__ import annotations
@@ -67,6 +68,12 @@ class KeypointFlow:
         check(self.lib.hs_flow_set_first_extracted(self.h, extractor.h, C.byref(n)))
         return n.value
 
+    def set_first_image(self, image, xy) -> int:
+        """The first frame with cvImgL from a hslam_amd.image.DeviceImage, device to device, and host keypoints."""
+        p = self._pts(xy)
+        check(self.lib.hs_flow_set_first_image(self.h, image.h, len(p), ptr(p)))
+        return len(p)
+
     def track(self, img8, max_l1_error: float) -> int:
         """One FindMatches against the new frame's cvImgL; returns the number of good points."""
         a = self._img(img8)
@@ -107,6 +114,12 @@ class KeypointFlow:
     def mean_flow(self) -> np.float32:
         m = C.c_float()
         check(self.lib.hs_flow_mean_flow(self.h, C.byref(m)))
+        return np.float32(m.value)
+
+    def mean_flow_device(self) -> np.float32:
+        """mean_flow()'s value made on the device: only the result is read back."""
+        m = C.c_float()
+        check(self.lib.hs_flow_mean_flow_device(self.h, C.byref(m)))
         return np.float32(m.value)
 
     def calc(self, prev8, next8, prev_xy, init_xy=None):

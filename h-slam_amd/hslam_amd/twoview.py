@@ -1,12 +1,14 @@
 """Initializer::FindTransformation (Src/Initializer.cpp:401-455) on the device through include/hs_twoview.h: the
 8-point H / F hypotheses of the caller's mvSets, their scores, the model choice, the 4 or 8 motion hypotheses, CheckRT,
-the decision and the median-depth scaling.  The draw of the sets stays the caller's (draw_sets restates the reference's
-loop over a numpy generator).
+the decision and the median-depth scaling.  The sets are the caller's (draw_sets restates the reference's loop over a
+numpy generator) or drawn on the device from the context's own cv::RNG-style generator (fit_flow_drawn).
 
     tv = TwoViewFit(capacity, (fx, fy, cx, cy))
     sets = draw_sets(200, status, np.random.default_rng(0))
     res = tv.fit(xy1, xy2, status, sets)            # host arrays; or
     res = tv.fit_flow(flow, sets)                   # FirstFramePts / MatchedPts / MatchedStatus where the flow holds them
+    tv.rng_skip(3 * nFeatures)                      # ColorVec's draws of a first frame
+    res = tv.fit_flow_drawn(flow, 200)              # the same with mvSets drawn on the device; tv.sets() reads them
     if res.ok: R, t = res.R, res.t                  # t already divided by the median depth
     g = tv.get()                                    # dict(inliers_h, inliers_f, scores_h, scores_f, triangulated, p3d, models)
     refiner.set_points_twoview(flow, tv)            # vbTriangulated and z, device to device
@@ -72,6 +74,7 @@ class TwoViewFit:
         self.capacity = int(capacity)
         self.n = 0
         self.n_sets = (0, 0)
+        self.n_fit_sets = 0
         k = (C.c_double * 4)(*[float(x) for x in K4])
         h = C.c_void_p()
         check(self.lib.hs_twoview_create(C.byref(h), device, self.capacity, k))
@@ -107,7 +110,7 @@ class TwoViewFit:
         s = self._sets(sets)
         res = TwoViewResult()
         check(self.lib.hs_twoview_fit(self.h, len(a), ptr(a), ptr(b), ptr(st), len(s), ptr(s), C.byref(res)))
-        self.n, self.n_sets = len(a), (len(s), len(s))
+        self.n, self.n_sets, self.n_fit_sets = len(a), (len(s), len(s)), len(s)
         return res
 
     def fit_flow(self, flow, sets) -> TwoViewResult:
@@ -117,8 +120,53 @@ class TwoViewFit:
         n = C.c_int()
         check(self.lib.hs_flow_get(flow.h, C.byref(n), *([None] * 6)))
         check(self.lib.hs_twoview_fit_flow(self.h, flow.h, len(s), ptr(s), C.byref(res)))
-        self.n, self.n_sets = n.value, (len(s), len(s))
+        self.n, self.n_sets, self.n_fit_sets = n.value, (len(s), len(s)), len(s)
         return res
+
+    def rng_seed(self, seed: int = 0):
+        """cv::RNG(seed): a seed of 0 becomes 0xffffffff.  A new TwoViewFit is seeded with 0."""
+        check(self.lib.hs_twoview_rng_seed(self.h, int(seed)))
+
+    def rng_skip(self, n_next: int):
+        """n_next draws thrown away (ColorVec takes 3 * nFeatures at every first frame)."""
+        check(self.lib.hs_twoview_rng_skip(self.h, int(n_next)))
+
+    def rng_state(self) -> int:
+        st = C.c_uint64()
+        check(self.lib.hs_twoview_rng_state(self.h, C.byref(st)))
+        return int(st.value)
+
+    def draw(self, status, n_sets: int):
+        """Parity entry: (mvSets (n_sets, 8) int32, m) drawn on the device over a host status array; advances the
+        generator."""
+        st = np.ascontiguousarray(status, np.uint8)
+        sets = np.zeros((max(int(n_sets), 1), 8), np.int32)
+        m = C.c_int()
+        check(self.lib.hs_twoview_draw(self.h, len(st), ptr(st), int(n_sets), ptr(sets), C.byref(m)))
+        return sets[:int(n_sets)].copy(), m.value
+
+    def fit_flow_drawn(self, flow, n_sets: int = 200) -> TwoViewResult:
+        """fit_flow with mvSets drawn on the device from the flow's MatchedStatus.  Fewer than 8 matched keys: ok 0,
+        why 5, the generator does not move.  reserved[0], reserved[1] of the record are the generator's state."""
+        res = TwoViewResult()
+        n = C.c_int()
+        check(self.lib.hs_flow_get(flow.h, C.byref(n), *([None] * 6)))
+        check(self.lib.hs_twoview_fit_flow_drawn(self.h, flow.h, int(n_sets), C.byref(res)))
+        if res.why != 5:
+            self.n, self.n_sets, self.n_fit_sets = n.value, (int(n_sets), int(n_sets)), int(n_sets)
+        return res
+
+    def sets(self) -> np.ndarray:
+        """mvSets of the last fit, drawn or uploaded: (n_sets, 8) int32."""
+        s = np.zeros((self.n_fit_sets, 8), np.int32)
+        check(self.lib.hs_twoview_get_sets(self.h, ptr(s)))
+        return s
+
+    def last_draw_stats(self):
+        """Device ms of the last draw's kernels: good_list, draw."""
+        ms = (C.c_double * 2)()
+        check(self.lib.hs_twoview_last_draw_stats(self.h, ms))
+        return dict(good_list=float(ms[0]), draw=float(ms[1]))
 
     def last_result(self) -> TwoViewResult:
         res = TwoViewResult()

@@ -101,6 +101,10 @@ int hs_flow_get(hs_flow* f, int* n, float* first_xy, float* prev_xy, float* xy, 
    accumulate into an int: acc = (int)(acc + norm), norm = (float)sqrt((double)dx^2 + (double)dy^2), the result
    (float)acc / (float)count (NaN when no point is good).  Before a track: HS_ERR_STATE. */
 int hs_flow_mean_flow(hs_flow* f, float* mean);
+/* The same value, bit for bit, made on the device: every norm in parallel, then the truncating accumulation as one
+   ordered chain in key order (it is not associative: the float sum rounds before the truncation).  The read-back is
+   the 4 bytes of the result. */
+int hs_flow_mean_flow_device(hs_flow* f, float* mean);
 
 /* One stand-alone calcOpticalFlowPyrLK between two given images (host) for n <= capacity points; init_xy nullable
    (no guess: the flow starts at prev_xy); xy_out[n][2], status_out[n], err_out[n] nullable.  Does not touch the

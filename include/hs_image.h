@@ -82,6 +82,9 @@ int hs_selector_make_maps_image(hs_selector* s, int frame_id, hs_image* im, floa
 int hs_extractor_extract_image(hs_extractor* e, hs_selector* s, hs_image* im, int* n_keys);
 /* hs_flow_track_u8: cvImgL. */
 int hs_flow_track_image(hs_flow* f, hs_image* im, float max_l1_error, int* n_good);
+/* hs_flow_set_first with TransitImage = cvImgL copied device to device; the keys xy[n][2] are the host's (a caller that
+   has its mvKeys from elsewhere than an extractor). */
+int hs_flow_set_first_image(hs_flow* f, hs_image* im, int n, const float* xy);
 /* hs_tracker_frame_to_ba without a tracker: level 0 becomes window frame `frame`'s image, the packed-texel refresh
    included, ordered on the device both ways. */
 int hs_image_to_ba(hs_image* im, hs_ctx* ba, int frame);

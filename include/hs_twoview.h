@@ -10,7 +10,8 @@
  * call is complete on the device when it returns.  Everything is allocated by hs_twoview_create; no later call
  * allocates.
  *
- * Not built: the cv::RNG draw of mvSets (the sets are the caller's), MatchIndirect, the stereo / RGBD initializers.
+ * Not built: MatchIndirect, the stereo / RGBD initializers.  ColorVec is not kept: only its draws are consumed
+ * (hs_twoview_rng_skip).
  *
  * Parity.  OpenCV is not a dependency of this project, so parity with cv::SVD is not pinned.  The contract below is
  * restated in numpy by tests/twoview_ref.py, which is what the kernels are held to.  Every deviation from the
@@ -53,6 +54,22 @@
  *           (float)((double)((float)acos((double)c) * 180.f) / pi); 0 when nothing passes.
  *   Decision.  csrc/hs_twoview_rule.h: ReconstructF's and ReconstructH's rules with minParallax = 1, minTriangulated =
  *           50; why = 3 or 4.
+ *   Generator (randomGen, cv::RNG(0)).  Parity with OpenCV is not pinned; tests/initializer_ref.py restates this contract.
+ *           State: one uint64_t.  seed(s): state = s ? s : 0xffffffff; create seeds with 0.
+ *           next(): state = (uint64_t)(uint32_t)state * 4164903690u + (uint32_t)(state >> 32); returns (uint32_t)state.
+ *           uniform(a, b): a == b ? a : (int)(next() % (unsigned)(b - a) + a); b is exclusive, a == b consumes no draw.
+ *           From seed 0 the first four next() are 0x07c09cf6, 0xb302a6a5, 0xe6abd4e7, 0x507b8a5d and the state is then
+ *           0xdfaf93c7507b8a5d (computed from this definition, a guard against 32- / 64-bit slips).
+ *   Draw of mvSets (:404-432).  all = the indices i with status[i] != 0, ascending; m = |all|.  For every set it =
+ *           0 .. n_sets-1: avail = all; for j = 0 .. 7: size = m - j; r = uniform(0, size - 1); sets[it][j] = avail[r];
+ *           avail[r] = avail[size - 1]; pop.  The generator runs on through all sets and across calls.  With m == 8
+ *           the eighth draw of every set is uniform(0, 0) and consumes nothing: 7 next() per set instead of 8.  m < 8
+ *           is undefined behaviour in the reference; here it is refused and the state does not move.  The host runs
+ *           the chain (8 * n_sets dependent multiply-adds at most) and uploads the 32-bit words; the list `all` and
+ *           the swap-and-pop are made on the device where the status is, and m comes back with the fit's one
+ *           read-back, from which the host knows how many words were consumed.
+ *   ColorVec (:55).  The first-frame branch draws 3 * nFeatures values uniform(0, 255) from the same generator: a first
+ *           frame advances the state by 3 * nFeatures next() calls (hs_twoview_rng_skip).
  *   Median depth (:1283-1297).  Index (size - 1) / 2 of the triangulated z, selected exactly; t and p3d are divided
  *           by it in fp32.  p3d is 0 where the key is not triangulated.
  */
@@ -73,7 +90,8 @@ typedef struct hs_twoview hs_twoview;
 typedef struct hs_twoview_result {
   int32_t ok;             /* 1: FindTransformation returned true */
   int32_t why;            /* 0 ok; 1 no hypothesis scored above 0; 2 H's singular values too close; 3 no clear winner or
-                             too few good points; 4 parallax below minParallax */
+                             too few good points; 4 parallax below minParallax; 5 fewer than 8 matched keys
+                             (hs_twoview_fit_flow_drawn only) */
   int32_t model;          /* 0 H, 1 F; -1 when why == 1 */
   int32_t best_h, best_f; /* the winning sets (-1: no set scored above 0) */
   int32_t n_inliers;      /* the chosen model's inliers (N of ReconstructH / ReconstructF) */
@@ -85,7 +103,8 @@ typedef struct hs_twoview_result {
   float median_depth;
   int32_t best_rt;        /* which of the 4 (F) or 8 (H) motion hypotheses won; -1: none */
   int32_t n_rt;           /* the motion hypotheses tested: 0, 4 or 8 */
-  int32_t reserved[6];
+  int32_t reserved[6];    /* after hs_twoview_fit_flow_drawn: [0], [1] = the low and the high 32 bits of the generator's
+                             state behind the call; 0 otherwise */
 } hs_twoview_result;      /* 128 bytes */
 
 /* capacity >= 8: the most keys of one fit.  K4 = fx, fy, cx, cy (rounded to fp32: the reference's K is CV_32F). */
@@ -103,6 +122,25 @@ int hs_twoview_fit(hs_twoview* tv, int n, const float* xy1, const float* xy2, co
    capacity keys (HS_ERR_INVALID) after a track (HS_ERR_STATE).  The status rule is checked on the device. */
 int hs_twoview_fit_flow(hs_twoview* tv, hs_flow* flow, int n_sets, const int32_t* sets, hs_twoview_result* result);
 
+/* The generator (the contract above).  The state belongs to the context and lives on the host; none of the three
+   touches the device.  n_next above 2^30: HS_ERR_INVALID (a skip is a host loop). */
+int hs_twoview_rng_seed(hs_twoview* tv, uint64_t seed);
+int hs_twoview_rng_skip(hs_twoview* tv, uint64_t n_next);
+int hs_twoview_rng_state(hs_twoview* tv, uint64_t* state);
+/* Parity entry: the draw alone over a host status[n], made by the kernels of hs_twoview_fit_flow_drawn; advances the
+   state; sets_out[n_sets][8]; *m_out (nullable) = the keys with status != 0 as the device counted them.  The last
+   fit and its read-backs are not touched.  HS_ERR_INVALID, the state unchanged: n outside 8 .. capacity, n_sets
+   outside 1 .. 256, fewer than 8 keys with status != 0. */
+int hs_twoview_draw(hs_twoview* tv, int n, const uint8_t* status, int n_sets, int32_t* sets_out, int* m_out);
+/* hs_twoview_fit_flow with the sets drawn on the device from the flow's MatchedStatus: no key-sized array and no
+   status byte crosses to the host, and the generator's new state comes back in the result record.  With fewer than 8
+   matched keys it returns HS_OK with result->ok = 0, why = 5, model, best_h, best_f and best_rt -1 and everything else
+   0 but the state words; the state does not move, no kernel of the fit runs, the parity read-backs keep the fit
+   before, and hs_refiner_set_points_twoview refuses until the next successful fit. */
+int hs_twoview_fit_flow_drawn(hs_twoview* tv, hs_flow* flow, int n_sets, hs_twoview_result* result);
+/* The sets of the last fit, drawn or uploaded: sets[n_sets][8].  Before a fit: HS_ERR_STATE. */
+int hs_twoview_get_sets(hs_twoview* tv, int32_t* sets);
+
 /* Parity read-backs of the last fit (or debug entry), all nullable: inliers_h[n], inliers_f[n] (the two winners'
    vbMatchesInliers), scores_h[n_sets], scores_f[n_sets], triangulated[n], p3d[n][3] (divided by the median depth),
    models[2][n_sets][9] (H21 of every set, then F21 of every set).  Before a fit: HS_ERR_STATE. */
@@ -118,6 +156,9 @@ int hs_twoview_get_rt(hs_twoview* tv, int* n_rt, int32_t* n_good, float* paralla
 /* Device time of the last fit's kernels in ms: ms[8] = normalize, hypotheses, scores, winners, decompose, CheckRT,
    select, finish. */
 int hs_twoview_last_stats(hs_twoview* tv, double* ms);
+/* Device time of the last draw's two kernels (hs_twoview_draw or hs_twoview_fit_flow_drawn) in ms: ms[2] = the list of
+   matched keys, the swap-and-pop.  Before a draw: HS_ERR_STATE. */
+int hs_twoview_last_draw_stats(hs_twoview* tv, double* ms);
 
 /* Debug entries that split the pipeline at its seams; both work on the keys of the last fit (HS_ERR_STATE before one),
    leave their outputs where hs_twoview_get / _get_rt read them, and end the validity of the last fit for
