@@ -229,6 +229,7 @@ struct LinConst {
   float th[HS_MAXF];
   float xad[HS_MAXF * 8];
   float cs[4];
+  int slot[HS_MAXF];  // window frame -> image slot
 };
 
 // kFix: System::linearizeAll(true)'s bookkeeping (Src/FullSystemOptimize.cpp:26-50): for every residual still active
@@ -285,11 +286,19 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
   const float thr = fmaxf(K.th[h], K.th[tc_]);  // std::max<float>(host TH, target TH)
   const float colorK = in.colorK, weightK = in.weightK;
   const HsPrecalc pc = K.pre[tc_];
-  // the target's image: selected from the kernel-argument pointers (uniform SGPRs), not loaded per lane
-  const float* timg3 = a.img3 + (long long)hs_img_slot(a.img_slot, tc_) * a.img_stride * 3;  // past the window: frame 0
+  // the target's image slot, staged with the block constants (one LDS read beside the precalc record's; the
+  // select chain over the kernel arguments cost 14 VALU and a kernarg load per point)
+  const float* timg3 = a.img3 + (long long)K.slot[tc_] * a.img_stride * 3;  // past the window: frame 0
   // the point's 8 residual-list slots and previous active mask, as scalars (uniform per point)
   const uint2 ro2 = make_uint2(__builtin_amdgcn_readfirstlane(in.ro2.x), __builtin_amdgcn_readfirstlane(in.ro2.y));
   auto res_slot = [&](int q) -> int { return (int)(int8_t)(((q < 4 ? ro2.x : ro2.y) >> (8 * (q & 3))) & 0xffu); };
+  // the list decoded once, per lane: entry k (the fused step, the slots' listed bits) and entry t (the per-point
+  // sums), and its length = the first negative entry, from one ballot over lanes 0..7 (octet 0, k = entry)
+  // (a lane-indexed pick between the two list words would be lowered to an indexed load from a stack copy: the
+  // byte is shifted out of the 64-bit list instead)
+  const unsigned long long ro64 = ((unsigned long long)ro2.y << 32) | ro2.x;
+  const int tq = (int)(int8_t)(ro64 >> (8 * k)), tl = (int)(int8_t)(ro64 >> (8 * t));
+  const int nres = __builtin_ctz(((unsigned)__ballot(tq < 0) & 0xffu) | 0x100u);
   // the previous linearization's per-point data for the fused step
   const unsigned fm = __builtin_amdgcn_readfirstlane(in.fm);
   const float xad = K.xad[tc_ * 8 + k];
@@ -311,21 +320,17 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     dot += cs2 * hcd.z;
     dot += cs3 * hcd.w;
     b -= dot;
-    // lane q gathers the dot of list entry q (one ds_bpermute), then the terms are subtracted in list order
-    const int tq = res_slot(k);
-    const float dq = __shfl(dsum, (tq < 0 ? 0 : tq) * 8 + 7);
+    // lane q gathers the dot of list entry q (one ds_bpermute), then the terms are subtracted in list order.  An
+    // entry past the list's end or of a slot outside the mask contributes +0 in place of being skipped: b - (+0) is
+    // b for every b (-0 and NaN included), so the eight subtractions need no per-entry decode, select or branch
+    const int tqs = tq < 0 ? 0 : tq;
+    const float dq = __shfl(dsum, tqs * 8 + 7);
+    const float dqm = (k < nres && ((m >> tqs) & 1u)) ? dq : 0.f;
     float dl[8];
 #pragma unroll
-    for (int q = 0; q < 8; q++) dl[q] = readlane_f(dq, q);  // independent, ahead of the ordered subtractions
-    bool live = true;
+    for (int q = 0; q < 8; q++) dl[q] = readlane_f(dqm, q);  // independent, ahead of the ordered subtractions
 #pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int tt = res_slot(q);
-      live = live && tt >= 0;
-      const int ts = tt < 0 ? 0 : tt;
-      const float bq = b - dl[q];
-      b = (live && ((m >> ts) & 1u)) ? bq : b;
-    }
+    for (int q = 0; q < 8; q++) b = b - dl[q];
     const float step = m != 0u ? -b * hdi : 0.f;
     idep = idep + 1.0f * step;
     idep0 = idep;
@@ -364,7 +369,10 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     const float new_idepth = idep0 * drescale;
     const float u = pt0 * drescale, v = pt1 * drescale;
     const float Ku = u * cal.fxl + cal.cxl, Kv = v * cal.fyl + cal.cyl;
-    okC = (drescale > 0) && (Ku > 1.1f && Kv > 1.1f && Ku < (cal.W - 3) && Kv < (cal.H - 3));
+    // the image bounds as floats, once: with the conversions out of the tests' operands the short-circuit form is
+    // lowered to compares and mask ANDs, not to nested exec-mask branches
+    const float wlim = (float)(cal.W - 3), hlim = (float)(cal.H - 3);
+    okC = drescale > 0 && Ku > 1.1f && Kv > 1.1f && Ku < wlim && Kv < hlim;
     centre[0] = Ku; centre[1] = Kv; centre[2] = new_idepth;
     const float* R0 = pc.R0;
     const float* t0 = pc.t0;
@@ -403,10 +411,11 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     Jy[8] = u * v * fy;
     Jy[9] = u * fy;
 
-    // pattern pixel k (staticPattern[8], Include/GlobalTypes.h:181-184) as selects: a lane-indexed
-    // constant-memory table would cost a dependent memory round trip here
-    const int pdx = (k == 1 || k == 6) ? -1 : (k == 2) ? 1 : (k == 3) ? -2 : (k == 5) ? 2 : 0;
-    const int pdy = (k == 0) ? -2 : (k <= 2) ? -1 : (k <= 5) ? 0 : (k == 6) ? 1 : 2;
+    // pattern pixel k (staticPattern[8], Include/GlobalTypes.h:181-184): pdx = (0, -1, 1, -2, 0, 2, -1, 0), pdy =
+    // (-2, -1, -1, 0, 0, 0, 1, 2), one signed nibble per pixel shifted out of a constant (a lane-indexed
+    // constant-memory table would cost a dependent memory round trip here, select trees become branches)
+    const int pdx = (int)(0x0F20E1F0u << (28 - 4 * k)) >> 28;
+    const int pdy = (int)(0x21000FFEu << (28 - 4 * k)) >> 28;
     const float px = pu + pdx, py = pv + pdy;
     float q0 = pc.KRKi[0] * px + pc.KRKi[1] * py + pc.KRKi[2] * 1.f;
     float q1 = pc.KRKi[3] * px + pc.KRKi[4] * py + pc.KRKi[5] * 1.f;
@@ -415,7 +424,8 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     q1 = q1 + pc.Kt[1] * idep;
     q2 = q2 + pc.Kt[2] * idep;
     const float PKu = q0 / q2, PKv = q1 / q2;
-    const bool okP = okC && (PKu > 1.1f && PKv > 1.1f && PKu < (cal.W - 3) && PKv < (cal.H - 3));
+    // (a NaN coordinate fails its upper-bound test, so the joint lower bound decides the same as the two single ones)
+    const bool okP = okC && fminf(PKu, PKv) > 1.1f && PKu < wlim && PKv < hlim;
     float3 hit = interp33p(timg3, okP ? PKu : 2.f, okP ? PKv : 2.f, cal.W);
     if (trc && threadIdx.x == 0 && hit.x != -12345.f) trc[(size_t)blockIdx.x * 16 + 13] = wall_clock64();
     const float color = colorK;
@@ -544,55 +554,75 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
   }
   if (t == nF - 1 && k == 0) a.newest_cand[p] = eval ? S[0] : -1.f;
   if (has && a.write_center && centreOk && k < 3) a.r_center[sl * 3 + k] = centre[k];
-  float tHdd, tbd, tc[4];  // the slot's terms of the per-point sums
+  float Xq;  // the slot's term of the per-point sums that this lane carries: tbd, tHdd, tc[0..3] on k = 0..5
   {
     // takeData (Include/OptimizationClasses.h:155-161), computed unconditionally, stored when active
     const float J00 = S[1], J11 = S[2], J10 = S[3];
     const float aa = J00 * Jd0 + J10 * Jd1;
     const float bb = J10 * Jd0 + J11 * Jd1;
-    tbd = S[12] * Jd0 + S[13] * Jd1;
-    tHdd = aa * Jd0 + bb * Jd1;
+    // tbd = S12 Jd0 + S13 Jd1, tHdd = aa Jd0 + bb Jd1, tc[c] = Jx[c] aa + Jy[c] bb: one two-product sum whose
+    // operands are picked per lane (the six sums computed under per-lane branches cost six exec-mask regions)
+    {
+      float u1 = Jx[0], u2 = Jy[0];
 #pragma unroll
-    for (int c = 0; c < 4; c++) tc[c] = Jx[c] * aa + Jy[c] * bb;
+      for (int c = 1; c < 4; c++) {
+        u1 = k == c + 2 ? Jx[c] : u1;
+        u2 = k == c + 2 ? Jy[c] : u2;
+      }
+      u1 = k == 0 ? S[12] : k == 1 ? aa : u1;
+      u2 = k == 0 ? S[13] : k == 1 ? bb : u2;
+      Xq = u1 * (k < 2 ? Jd0 : aa) + u2 * (k < 2 ? Jd1 : bb);
+    }
     float jx4 = Jx[4], jy4 = Jy[4];
 #pragma unroll
     for (int c = 5; c < 10; c++) {
       jx4 = k == c - 4 ? Jx[c] : jx4;
       jy4 = k == c - 4 ? Jy[c] : jy4;
     }
-    const float jj = k < 6 ? jx4 * aa + jy4 * bb : (k == 6 ? S[4] * Jd0 + S[5] * Jd1 : S[6] * Jd0 + S[7] * Jd1);
+    // JpJdF[k] = Jx[4 + k] aa + Jy[4 + k] bb (k < 6), S4 Jd0 + S5 Jd1 (6), S6 Jd0 + S7 Jd1 (7), picked likewise
+    jx4 = k < 6 ? jx4 : k == 6 ? S[4] : S[6];
+    jy4 = k < 6 ? jy4 : k == 6 ? S[5] : S[7];
+    const float jj = jx4 * (k < 6 ? aa : Jd0) + jy4 * (k < 6 ? bb : Jd1);
     if (active) a.p_JpJdF[(p * 8 + t) * 8 + k] = jj;
     o.jj = active ? jj : 0.f;
   }
-  // ---------------- per-point sums in the point's residual-list order (uniform; readlane from lane 8 * slot)
+  // ---------------- per-point sums in the point's residual-list order (one lane per quantity; the results by readlane)
   {
     const unsigned long long actBits = __ballot(active);
-    // lane 8t + i carries quantity i of slot t (tbd, tHdd, tc[0..3], -, econ); lane i of every octet gathers
-    // quantity i of the listed residuals (one ds_bpermute per list entry, all in flight), then sums them in list
-    // order: the reference's sequential sums, one lane per quantity
-    const float X = k == 0 ? tbd : k == 1 ? tHdd : k == 2 ? tc[0] : k == 3 ? tc[1] : k == 4 ? tc[2] : k == 5 ? tc[3] : econ;
-    float g[8];
-    int nres = 8;
-#pragma unroll
-    for (int qn = 0; qn < 8; qn++) {
-      const int tt = res_slot(qn);
-      nres = (tt < 0 && qn < nres) ? qn : nres;
-      g[qn] = __shfl(X, (tt < 0 ? 0 : tt) * 8 + k);
-    }
+    // lane 8t + i carries quantity i of slot t (tbd, tHdd, tc[0..3], -, econ); lane i of every octet ends up with
+    // quantity i of the listed residuals and sums them in list order: the reference's sequential sums, one lane per
+    // quantity
+    const float X = k < 6 ? Xq : econ;
+    // A term that the reference skips (a quantity of an inactive residual, anything past the list's end) enters
+    // as +0: both sums start at +0, so neither is ever -0, and s + (+0) is s.  The gate is therefore applied to the
+    // values -- at the source lane for the residual's active flag, at the gathering lane for the list's end --
+    // and the sums themselves are eight unconditional adds.  Octet t gathers list entry t (one ds_bpermute for
+    // the whole list), the 64 values go through the wave's scratch (the pattern rows, free since the folds) and
+    // every lane reads the eight entries of its quantity k.
+    const float Xg = (k >= 6 || active) ? X : 0.f;
+    float G = __shfl(Xg, (tl < 0 ? 0 : tl) * 8 + k);
+    G = t < nres ? G : 0.f;
+    float* gs = ws + LW_QS;
+    gs[k * 8 + t] = G;
+    __builtin_amdgcn_wave_barrier();
+    const float4 g0 = *reinterpret_cast<const float4*>(gs + k * 8), g1 = *reinterpret_cast<const float4*>(gs + k * 8 + 4);
+    const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    __builtin_amdgcn_wave_barrier();  // the rows are the next point's pattern rows: its stores stay behind these reads
     float qsum = 0.f;
     double eAcc = 0.0;
-    unsigned mask = 0u;
 #pragma unroll
-    for (int qn = 0; qn < 8; qn++) {  // fully unrolled, predicated (g stays in registers)
-      const bool listed = qn < nres;  // uniform
-      const int tt = res_slot(qn) & 7;
-      const double e1 = eAcc + (double)g[qn];  // econ: every listed residual (read from lane 7)
-      eAcc = listed ? e1 : eAcc;
-      const bool act = listed && ((actBits >> (tt * 8)) & 1ull);
-      mask |= act ? 1u << tt : 0u;
-      const float q1 = qsum + g[qn];
-      qsum = act ? q1 : qsum;
+    for (int qn = 0; qn < 8; qn++) {
+      eAcc = eAcc + (double)g[qn];  // econ: every listed residual (read from lane 7)
+      qsum = qsum + g[qn];
     }
+    // the active mask: slot t is listed when one of the first nres entries names it; byte t of (listed & active)
+    // is folded to its bit 0 and the eight bits are gathered by one multiply
+    unsigned long long am = __ballot(k < nres && (tq & 7) == t) & actBits;
+    am |= am >> 4;
+    am |= am >> 2;
+    am |= am >> 1;
+    am &= 0x0101010101010101ull;
+    const unsigned mask = (unsigned)((am * 0x0102040810204080ull) >> 56);
     const double eSum = __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(__double_as_longlong(eAcc) >> 32), 7) << 32) |
                                              (unsigned int)__builtin_amdgcn_readlane((int)__double_as_longlong(eAcc), 7));
     const float bd = readlane_f(qsum, 0), Hdd = readlane_f(qsum, 1);
@@ -613,6 +643,14 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     float4 hc4;
     if (kMarg && a.marg) hc4 = make_float4(0.f + Hcd[0], 0.f + Hcd[1], 0.f + Hcd[2], 0.f + Hcd[3]);
     else hc4 = make_float4(Hcd[0] + 0.f, Hcd[1] + 0.f, Hcd[2] + 0.f, Hcd[3] + 0.f);
+    {
+      // Hcd[r], Hcd[c] of the accHcc / accbc lane (r, c) = ((lane >> 2) & 3, lane & 3): lane 2 + i holds Hcd[i] as
+      // its qsum, so the same sum with 0 is formed there and picked by lane address (two ds_bpermute) -- a select
+      // over the four uniform values becomes nested exec-mask branches
+      const float qh = (kMarg && a.marg) ? 0.f + qsum : qsum + 0.f;
+      o.hcr = __shfl(qh, 2 + ((lane >> 2) & 3));
+      o.hcc = __shfl(qh, 2 + (lane & 3));
+    }
     if (lane == 0) {
       a.p_actmask[p] = (uint8_t)mask;
       a.p_HdiF[p] = HdiF;
@@ -678,9 +716,6 @@ __device__ __forceinline__ void lin_point(const HsLinArgs& a, int p, int h, int 
     o.t014 = kk == 0 ? S[4] : (kk == 1 ? S[6] : S[12]);
     o.t114 = kk == 0 ? S[5] : (kk == 1 ? S[7] : S[13]);
     o.br15 = k == 0 ? S[8] : k == 1 ? S[9] : k == 2 ? S[14] : k == 3 ? S[10] : k == 4 ? S[15] : S[16];
-    const int r = (lane >> 2) & 3, c = lane & 3;
-    o.hcr = r == 0 ? o.Hcd[0] : r == 1 ? o.Hcd[1] : r == 2 ? o.Hcd[2] : o.Hcd[3];
-    o.hcc = c == 0 ? o.Hcd[0] : c == 1 ? o.Hcd[1] : c == 2 ? o.Hcd[2] : o.Hcd[3];
   }
 }
 
@@ -801,6 +836,7 @@ __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
       K.xad[tid] = s1 + s2;
     }
     if (tid < 4) K.cs[tid] = a.st->cstep[tid];
+    if (tid >= 128 && tid < 128 + HS_MAXF) K.slot[tid - 128] = hs_img_slot(a.img_slot, tid - 128);
     constexpr int CW = (int)(sizeof(HsCalib) / 4);
     static_assert(sizeof(HsCalib) % 4 == 0, "calib staged as words");
     if (tid >= 64 && tid < 64 + CW)
@@ -829,12 +865,21 @@ __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
     if (a.accumulate) acc_point<kExact>(A, P, h, lane, ws);
   } else if (work) {
     for (int p = pb + wv; p < pe; p += a.W) {  // wave-uniform
+      // the argument block (472 bytes: about 38 pointers, the tables and the uniform terms) is re-read through a
+      // pointer the optimizer cannot see through, once per point: its words are then loaded where they are used
+      // (scalar loads from the kernarg segment) instead of being hoisted out of the loop and kept live across the
+      // point's work in spilled SGPRs.  This reads the kernarg segment at offset 0, not `a`: lin_block is only for
+      // kernels whose single parameter is the HsLinArgs they pass on (the wrappers below)
+      typedef const HsLinArgs __attribute__((address_space(4))) * KArgs;
+      KArgs ap = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();  // the kernel's only argument
+      asm volatile("" : "+s"(ap));
+      const HsLinArgs& al = *(const HsLinArgs*)ap;
       LinIn nxt;
-      if (p + a.W < pe) lin_load(a, p + a.W, lane, nxt);  // the next point's loads overlap this point's work
+      if (p + al.W < pe) lin_load(al, p + al.W, lane, nxt);  // the next point's loads overlap this point's work
       else nxt = cur;  // last point of the wave (a wave-uniform branch): no duplicate loads
       LinPt P;
-      lin_point<kFix, kMarg, kProd>(a, p, h, lane, cur, K, ws, P);
-      if (a.accumulate) acc_point<kExact>(A, P, h, lane, ws);
+      lin_point<kFix, kMarg, kProd>(al, p, h, lane, cur, K, ws, P);
+      if (al.accumulate) acc_point<kExact>(A, P, h, lane, ws);
       cur = nxt;
     }
   }
@@ -875,14 +920,24 @@ __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
   for (int k = 0; k < NI; k++) {
     const int i = tid + k * HS_LIN_NT;
     float4 s = v[k][0];
+    if (a.W == HS_LIN_NW) {  // production: every wave takes points, so the sums carry no per-wave select
 #pragma unroll
-    for (int w = 1; w < HS_LIN_NW; w++)
-      if (w < a.W) {
+      for (int w = 1; w < HS_LIN_NW; w++) {
         s.x += v[k][w].x;
         s.y += v[k][w].y;
         s.z += v[k][w].z;
         s.w += v[k][w].w;
       }
+    } else {
+#pragma unroll
+      for (int w = 1; w < HS_LIN_NW; w++)
+        if (w < a.W) {
+          s.x += v[k][w].x;
+          s.y += v[k][w].y;
+          s.z += v[k][w].z;
+          s.w += v[k][w].w;
+        }
+    }
     if (i < NE * 16) out4[i] = s;
   }
   if (tid < 3) {
@@ -894,6 +949,9 @@ __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
 }
 }  // namespace
 
+// lin_block's point loop re-reads HsLinArgs from offset 0 of the kernarg segment: these wrappers take the block by
+// value as their only parameter, and a wrapper that is added takes it the same way
+static_assert(std::is_trivially_copyable<HsLinArgs>::value && sizeof(HsLinArgs) <= 4096, "HsLinArgs by value in the kernarg segment");
 __global__ __launch_bounds__(HS_LIN_NT) void hs_k_lin(HsLinArgs a) { lin_block<false, false, false, true>(a); }
 __global__ __launch_bounds__(HS_LIN_NT) void hs_k_lin_gen(HsLinArgs a) { lin_block<false, false>(a); }
 __global__ __launch_bounds__(HS_LIN_NT) void hs_k_lin_exact(HsLinArgs a) { lin_block<true, false>(a); }
