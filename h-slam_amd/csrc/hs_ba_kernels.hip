@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <cstddef>
 #include <type_traits>
 
 #include "hs_kernels.h"
@@ -796,51 +797,140 @@ __device__ __forceinline__ void acc_point(LinAcc<kExact>& A, const LinPt& P, int
   A.np += 1.0;
 }
 
+// Every kernel-argument word that lin_block's prologue and the first lin_load read, named in the entry block: the
+// compiler otherwise loads an argument where it is first used, one wait on the kernarg segment per group of uses and
+// each a round trip of its own when it touches a new cache line; used here, they are loaded together with the host
+// and block tables and waited for once (hs_k_lin's prologue as one round trip).
+__device__ __forceinline__ void lin_args_touch(const HsLinArgs& a) {
+  asm volatile("" ::"s"(a.st), "s"(a.nF), "s"(a.pre), "s"(a.frameTH), "s"(a.adHostF), "s"(a.adTargetF), "s"(a.W), "s"(a.brk));
+  asm volatile("" ::"s"(a.idepth), "s"(a.idepth_zero), "s"(a.u), "s"(a.v), "s"(a.res_of_slot), "s"(a.r_state),
+               "s"(a.r_energy), "s"(a.r_newEnergy), "s"(a.color), "s"(a.weight), "s"(a.res_order), "s"(a.p_actmask),
+               "s"(a.p_JpJdF), "s"(a.p_bdSumF), "s"(a.p_HdiF_prev), "s"(a.p_Hcd), "s"(a.priorF));
+}
+
 template <bool kExact, bool kFix, bool kMarg = false, bool kProd = false>
 __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
   struct { long long* trace; } const T{kProd ? nullptr : a.trace};  // HS_TRACE's view
   extern __shared__ float lin_stage[];  // [HS_LIN_NW waves][ne][64] fp32 partials, then [HS_LIN_NW][3] fp64 energies
+  lin_args_touch(a);
   // the wave index as a scalar: the point index and everything per point then stays uniform (scalar loads,
   // scalar branches) instead of being treated as divergent
-  if (a.brk && a.st->stop) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x;
-  int h = 0;  // the block's host: from the kernel-argument block boundaries, no load
+  const int b = blockIdx.x, nF = a.nF;
+  // the block's host, its blocks and its points: from the kernel-argument tables by selects, no load (an index
+  // into the tables that depends on h would be a second round trip to the kernarg segment)
+  int h = 0;
 #pragma unroll
-  for (int i = 1; i < HS_MAXF; i++) h += (i < a.nF && b >= a.blk_begin[i]) ? 1 : 0;
-  const int nb = a.blk_begin[h + 1] - a.blk_begin[h], q = b - a.blk_begin[h];
-  const int hb = a.host_begin[h], nh = a.host_begin[h + 1] - hb;
-  const int pb = hb + (int)((long long)nh * q / nb), pe = hb + (int)((long long)nh * (q + 1) / nb);
+  for (int i = 1; i < HS_MAXF; i++) h += (i < nF && b >= a.blk_begin[i]) ? 1 : 0;
+  int bb = a.blk_begin[0], be = a.blk_begin[1], hb = a.host_begin[0], he = a.host_begin[1];
+#pragma unroll
+  for (int i = 1; i < HS_MAXF; i++) {
+    bb = h == i ? a.blk_begin[i] : bb;
+    be = h == i ? a.blk_begin[i + 1] : be;
+    hb = h == i ? a.host_begin[i] : hb;
+    he = h == i ? a.host_begin[i + 1] : he;
+  }
+  const int nb = be - bb, q = b - bb, nh = he - hb;
   HS_TRACE(T, 0);
+  // The prologue is ONE memory round trip: the stop word, the wave's first point and every load of the block's
+  // constants (precalc records of host h by target, thresholds, the adjoints and frame steps of xAd[h][.][.],
+  // calib, calib step, image slots) are requested into registers before the first wait on any of them; the LDS
+  // stores follow.  Each load is unconditional at a clamped index and its store is predicated.  The constants are
+  // spread over the waves by wave-uniform tests, one word per lane: precalc words on waves 4-7, calib on wave 2,
+  // thresholds, calib step and image slots on wave 3, xAd's 32 operands per lane on wave 1; wave 0 requests
+  // nothing but its point.  Words at a block-uniform address are indexed through a zero the compiler cannot see,
+  // so they are vector loads: as scalar loads their wait would share lgkmcnt with the LDS stores.  The empty asm
+  // statement with a memory clobber keeps the loads where they are written (a load whose only consumer is a
+  // predicated store is otherwise sunk into the store's branch, behind the other loads' waits); the ones with
+  // "+v" operands keep the consumers behind the batch.
   __shared__ LinConst K;
-  {  // the block's constants: precalc records of host h (by target), thresholds, xAd[h][.][.], calib step
-    const int nF = a.nF;
-    constexpr int PW = (int)(sizeof(HsPrecalc) / 4);
-    static_assert(sizeof(HsPrecalc) % 4 == 0, "precalc staged as words");
-    const int* src = reinterpret_cast<const int*>(a.pre + h * nF);
-    int* dst = reinterpret_cast<int*>(K.pre);
-    for (int i = tid; i < nF * PW; i += HS_LIN_NT) dst[i] = src[i];
-    if (tid < nF) K.th[tid] = a.frameTH[tid];
-    if ((kProd || a.fuse_step) && tid < nF * 8) {
-      // xAd[h][t][c] of the last solve (EnergyFunctional::resubstituteF_MT): the frame steps (float)lastX and the
-      // fp32 adjoints of the pair, in the solve's summation order
-      const int t = tid >> 3, c = tid & 7;
-      const float* aH = a.adHostF + (h + nF * t) * 64;
-      const float* aT = a.adTargetF + (h + nF * t) * 64;
-      const double* lx = a.st->lastX;
-      float s1 = 0.f, s2 = 0.f;
+  constexpr int PW = (int)(sizeof(HsPrecalc) / 4), CW = (int)(sizeof(HsCalib) / 4);
+  static_assert(sizeof(HsPrecalc) % 4 == 0 && sizeof(HsCalib) % 4 == 0, "precalc and calib staged as words");
+  static_assert(HS_LIN_NW == 8 && HS_MAXF * PW <= 4 * 64 && HS_MAXF * 8 <= 64 && CW <= 64 && HS_MAXF <= 8,
+                "the prologue's roles: one word per lane");
+  static_assert(offsetof(LinConst, pre) % 4 == 0 && offsetof(LinConst, th) % 4 == 0 &&
+                    offsetof(LinConst, cs) % 4 == 0 && offsetof(LinConst, slot) % 4 == 0,
+                "LinConst staged as words");
+  const bool fuse = kProd || a.fuse_step;
+  int vz;
+  asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
+  // (global pointers by type: with the argument block among the sources they would otherwise merge to generic
+  // ones, whose flat loads count on lgkmcnt as well)
+  typedef const int __attribute__((address_space(1))) * GInt;
+  const GInt stw = (GInt)(&a.st->stop + vz);
+  const int stopw = *stw;  // the oldest load of the batch: the first one waited for
+  const int pb = hb + (int)((long long)nh * q / nb), pe = hb + (int)((long long)nh * (q + 1) / nb);
+  LinIn cur;
+  const bool work = wv < a.W && pb + wv < pe;
+  // the wave's first point (a wave without one: the host's last point, not used), in flight across the barrier
+  lin_load(a, max(min(pb + wv, he - 1), 0), lane, cur);
+  // the lane's word: its source (in bounds on every lane), its place in K (in words) and whether it is stored
+  GInt src = stw;
+  int dsti = 0;
+  bool sto = false;
+  if (wv >= 4) {
+    const int i = tid - 4 * 64;
+    src = (GInt)reinterpret_cast<const int*>(a.pre + h * nF) + min(i, nF * PW - 1);
+    dsti = (int)(offsetof(LinConst, pre) / 4) + i;
+    sto = i < nF * PW;
+  } else if (wv == 2) {
+    src = (GInt)reinterpret_cast<const int*>(&a.st->dcal) + min(lane, CW - 1);
+    dsti = (int)(offsetof(LinConst, cal) / 4) + lane;
+    sto = lane < CW;
+  } else if (wv == 3) {
+    // lanes 0-7 the thresholds, 8-11 the calib step, 16-23 the image slots: the kernel's own argument block (the
+    // only argument, at offset 0 of the kernarg segment), read per lane like the other words -- hs_img_slot's
+    // select chain over the arguments is compiled into such a load as well, but a dependent one
+    const GInt ks = (GInt)reinterpret_cast<const int*>(
+        reinterpret_cast<const char*>((const void*)__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(HsLinArgs, img_slot));
+    const int j = lane & 7;
+    src = lane < 8 ? (GInt)reinterpret_cast<const int*>(a.frameTH) + min(j, nF - 1)
+                   : lane < 16 ? (GInt)reinterpret_cast<const int*>(a.st->cstep) + (j & 3) : ks + j;
+    dsti = lane < 8 ? (int)(offsetof(LinConst, th) / 4) + j
+                    : lane < 16 ? (int)(offsetof(LinConst, cs) / 4) + (j & 3) : (int)(offsetof(LinConst, slot) / 4) + j;
+    sto = lane < 8 ? j < nF : lane < 16 ? j < 4 : lane < 16 + HS_MAXF;
+  }
+  int cw = *src;
+  // xAd (wave 1): the pair's fp32 adjoint columns and the frame steps of host and target (16 B loads kept whole
+  // up to their use: merged from single loads, their halves are copied apart right behind the loads, which waits)
+  typedef double d2 __attribute__((ext_vector_type(2), aligned(8)));
+  float xaH[8], xaT[8];
+  d2 xlH[4], xlT[4];
+  const bool xad = wv == 1 && fuse;
+  if (xad) {
+    const int t = min(lane >> 3, nF - 1), c = lane & 7;
+    const float* aH = a.adHostF + (h + nF * t) * 64 + c;
+    const float* aT = a.adTargetF + (h + nF * t) * 64 + c;
+    const d2* lH = reinterpret_cast<const d2*>(a.st->lastX + 4 + 8 * h + vz);
+    const d2* lT = reinterpret_cast<const d2*>(a.st->lastX + 4 + 8 * t);
 #pragma unroll
-      for (int rr = 0; rr < 8; rr++) s1 += (float)lx[4 + 8 * h + rr] * aH[rr * 8 + c];
-#pragma unroll
-      for (int rr = 0; rr < 8; rr++) s2 += (float)lx[4 + 8 * t + rr] * aT[rr * 8 + c];
-      K.xad[tid] = s1 + s2;
+    for (int rr = 0; rr < 8; rr++) {
+      xaH[rr] = aH[rr * 8];
+      xaT[rr] = aT[rr * 8];
     }
-    if (tid < 4) K.cs[tid] = a.st->cstep[tid];
-    if (tid >= 128 && tid < 128 + HS_MAXF) K.slot[tid - 128] = hs_img_slot(a.img_slot, tid - 128);
-    constexpr int CW = (int)(sizeof(HsCalib) / 4);
-    static_assert(sizeof(HsCalib) % 4 == 0, "calib staged as words");
-    if (tid >= 64 && tid < 64 + CW)
-      reinterpret_cast<int*>(&K.cal)[tid - 64] = reinterpret_cast<const int*>(&a.st->dcal)[tid - 64];
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+      xlH[rr] = lH[rr];
+      xlT[rr] = lT[rr];
+    }
+  }
+  asm volatile("" ::: "memory");
+  // optimize's device-side break: block-uniform, before any store and before the barrier
+  if (a.brk && __builtin_amdgcn_readfirstlane(stopw)) return;
+  asm volatile("" : "+v"(cw));
+  if (sto) reinterpret_cast<int*>(&K)[dsti] = cw;
+  if (xad) {
+    // xAd[h][t][c] of the last solve (EnergyFunctional::resubstituteF_MT): the frame steps (float)lastX and the
+    // fp32 adjoints of the pair, in the solve's summation order
+    asm volatile("" : "+v"(xaH[0]), "+v"(xaH[1]), "+v"(xaH[2]), "+v"(xaH[3]), "+v"(xaH[4]), "+v"(xaH[5]), "+v"(xaH[6]), "+v"(xaH[7]),
+                      "+v"(xaT[0]), "+v"(xaT[1]), "+v"(xaT[2]), "+v"(xaT[3]), "+v"(xaT[4]), "+v"(xaT[5]), "+v"(xaT[6]), "+v"(xaT[7]));
+    asm volatile("" : "+v"(xlH[0]), "+v"(xlH[1]), "+v"(xlH[2]), "+v"(xlH[3]), "+v"(xlT[0]), "+v"(xlT[1]), "+v"(xlT[2]), "+v"(xlT[3]));
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int rr = 0; rr < 8; rr++) s1 += (float)xlH[rr >> 1][rr & 1] * xaH[rr];
+#pragma unroll
+    for (int rr = 0; rr < 8; rr++) s2 += (float)xlT[rr >> 1][rr & 1] * xaT[rr];
+    if (lane < nF * 8) K.xad[lane] = s1 + s2;
   }
   LinAcc<kExact> A;
 #pragma unroll
@@ -852,9 +942,6 @@ __device__ __forceinline__ void lin_block(const HsLinArgs& a) {
   A.C = 0.f;
   A.e = A.sid = A.np = 0.0;
   float* ws = lin_stage + wv * hs_ne(kExact) * 64;  // the wave's LDS scratch (its partials area)
-  LinIn cur;
-  const bool work = wv < a.W && pb + wv < pe;
-  if (work) lin_load(a, pb + wv, lane, cur);  // in flight across the barrier
   __syncthreads();
   HS_TRACE(T, 12);
   if (work && pb + wv + a.W >= pe) {
@@ -1355,6 +1442,10 @@ __device__ __forceinline__ void red_host_chunk(const HsRedArgs& a, int h, int q)
 }
 
 __global__ __launch_bounds__(256) void hs_k_reduce(HsRedArgs a) {
+  // the entry's kernel arguments, named here so that they are loaded together (one wait on the kernarg segment
+  // instead of one each for stop, hist_only, nF / Q and the host chunk's pointers)
+  asm volatile("" ::"s"(a.stop), "s"(a.hist_only), "s"(a.nF), "s"(a.Q), "s"(a.ne), "s"(a.nblk), "s"(a.part),
+               "s"(a.hostsum), "s"(a.trace));
   if (a.stop && *a.stop) return;
   const int nred = a.nF * a.Q;
   const int b = blockIdx.x;
