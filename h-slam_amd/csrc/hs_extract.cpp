@@ -1,6 +1,7 @@
 // hs_extract.cpp — the extractor context of include/hs_extract.h: argument checks, the blur weights and umax by
 // their rules on the host, and one extract as a chain of launches on the extractor's stream that ends in the single
-// 4-byte read of the key count.
+// 4-byte read of the key count.  The keys come from the selection map (run_extract) or from the corner detector
+// (run_fast, hs_fast_kernels.hip); the blur, the descriptors and the closing read are shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include "../../include/hs_ba.h"
 #include "../../include/hs_extract.h"
 #include "hs_extract_kernels.h"
+#include "hs_fast_kernels.h"
 #include "../../include/hs_image.h"
 #include "hs_host.h"
 #include "hs_image_kernels.h"
@@ -22,6 +24,13 @@ struct hs_extract_result {
   float *x = nullptr, *y = nullptr, *angle = nullptr;
   uint32_t* desc = nullptr;
   uint8_t* blurred = nullptr;
+  // the UseFAST branch (allocated by the first fast extract): mvKeys[i].response, the corners before Ssc in sorted
+  // order, and {corners, width taken, corners taken}
+  float* response = nullptr;
+  int* s_idx = nullptr;
+  uint8_t* s_resp = nullptr;
+  int* info = nullptr;
+  bool fast = false;  // this set holds a fast extract
 };
 
 struct hs_extractor : hs::Device {
@@ -43,6 +52,15 @@ struct hs_extractor : hs::Device {
   int cur = 0;  // res[cur] is the last successful extract
   int n = 0;
   float last_ms = 0;
+  // scratch of the UseFAST branch, allocated by the first fast extract
+  bool have_fast = false;
+  int max_corners = 0;  // strict 3x3 maxima of a W x H plane with a 3-px band: no two are 8-neighbours
+  uint8_t *d_resp = nullptr, *d_cresp = nullptr, *d_covered = nullptr, *d_occ = nullptr;
+  int *d_frow_cnt = nullptr, *d_cidx = nullptr;
+  int max_high = 0;  // Ssc evaluates the widths 1 .. max_high of a search, each in its own workgroup
+  int *d_wtaken = nullptr, *d_wcnt = nullptr;
+  size_t *d_woff = nullptr, *d_toff = nullptr;
+  std::vector<size_t> h_toff;
 };
 
 namespace {
@@ -80,13 +98,9 @@ unsigned long long make_umax() {
   return p;
 }
 
-// everything after the inputs are on the device (or enqueued on e->stream): the kernels into the spare result set,
-// the count's read, the swap.  d_map_src: the map to scan (the extractor's own or the selector's).
-int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, const uint8_t* raw, int* n_keys) {
-  hs_extract_result& r = e->res[e->cur ^ 1];
+// the launches both branches share: cvImgL's blur into the result set ...
+int launch_blur(hs_extractor* e, hs_extract_result& r) {
   hipStream_t s = e->stream;
-  HS_HIP(hipEventRecord(e->e0, s));
-  if (u) HS_HIP(hs_undist_enqueue(u, s, raw, nullptr, e->d_img));
   HsExtBlurArgs b;
   b.W = e->W;
   b.H = e->H;
@@ -96,6 +110,57 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
   hipLaunchKernelGGL(hs_k_ext_blur, dim3((e->W + kExtBlurTileW - 1) / kExtBlurTileW, (e->H + kExtBlurTileH - 1) / kExtBlurTileH),
                      dim3(256), 0, s, b);
   HS_HIP(hipGetLastError());
+  return HS_OK;
+}
+
+// angle and descriptor of the keys that lie in r.x / r.y, their count in d_count
+int launch_desc(hs_extractor* e, hs_extract_result& r) {
+  HsExtDescArgs d;
+  d.W = e->W;
+  d.cap = e->alloc;
+  d.umax = e->umax;
+  d.count = e->d_count;
+  d.x = r.x;
+  d.y = r.y;
+  d.img = e->d_img;
+  d.blurred = r.blurred;
+  d.pattern = e->d_pattern;
+  d.angle = r.angle;
+  d.desc = r.desc;
+  // a wave per key over a grid that does not depend on the count: the count is read on the device
+  hipLaunchKernelGGL(hs_k_ext_desc, dim3(std::min((d.cap + 3) / 4, 2048)), dim3(256), 0, e->stream, d);
+  HS_HIP(hipGetLastError());
+  return HS_OK;
+}
+
+// the closing event, the count's read and the one wait; on success the spare set becomes the result
+int finish_extract(hs_extractor* e, int* n_keys, bool fast) {
+  hipStream_t s = e->stream;
+  HS_HIP(hipEventRecord(e->e1, s));
+  HS_HIP(hipMemcpyAsync(e->h_count, e->d_count, sizeof(int), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));  // the one wait of an extract
+  e->have_img = true;
+  HS_HIP(hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
+  const int n = *e->h_count;
+  if (n_keys) *n_keys = n;
+  if (n > e->cap)
+    return hs::fail(HS_ERR_INVALID, "extract yields " + std::to_string(n) + " keys, capacity is " + std::to_string(e->cap));
+  // (n <= alloc = min(cap, interior) here.  A fast extract's keys may lie on x = W-19 / y = H-19, outside the
+  // interior, but they are strict 3x3 maxima: at most ceil((W-37)/2) * ceil((H-37)/2) <= (W-38) * (H-38) of them.)
+  e->cur ^= 1;
+  e->n = n;
+  e->res[e->cur].fast = fast;
+  return HS_OK;
+}
+
+// everything after the inputs are on the device (or enqueued on e->stream): the kernels into the spare result set,
+// the count's read, the swap.  d_map_src: the map to scan (the extractor's own or the selector's).
+int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, const uint8_t* raw, int* n_keys) {
+  hs_extract_result& r = e->res[e->cur ^ 1];
+  hipStream_t s = e->stream;
+  HS_HIP(hipEventRecord(e->e0, s));
+  if (u) HS_HIP(hs_undist_enqueue(u, s, raw, nullptr, e->d_img));
+  HS_TRY(launch_blur(e, r));
   HsExtKeysArgs k;
   k.W = e->W;
   k.H = e->H;
@@ -110,33 +175,122 @@ int run_extract(hs_extractor* e, const float* d_map_src, hs_undistorter* u, cons
   HS_HIP(hipGetLastError());
   hipLaunchKernelGGL(hs_k_ext_write, dim3((rows + 3) / 4), dim3(256), 0, s, k);
   HS_HIP(hipGetLastError());
-  HsExtDescArgs d;
-  d.W = e->W;
-  d.cap = k.cap;
-  d.umax = e->umax;
-  d.count = e->d_count;
-  d.x = r.x;
-  d.y = r.y;
-  d.img = e->d_img;
-  d.blurred = r.blurred;
-  d.pattern = e->d_pattern;
-  d.angle = r.angle;
-  d.desc = r.desc;
-  // a wave per key over a grid that does not depend on the count: the count is read on the device
-  hipLaunchKernelGGL(hs_k_ext_desc, dim3(std::min((k.cap + 3) / 4, 2048)), dim3(256), 0, s, d);
-  HS_HIP(hipGetLastError());
-  HS_HIP(hipEventRecord(e->e1, s));
-  HS_HIP(hipMemcpyAsync(e->h_count, e->d_count, sizeof(int), hipMemcpyDeviceToHost, s));
-  HS_HIP(hipStreamSynchronize(s));  // the one wait of an extract
-  e->have_img = true;
-  HS_HIP(hipEventElapsedTime(&e->last_ms, e->e0, e->e1));
-  const int n = *e->h_count;
-  if (n_keys) *n_keys = n;
-  if (n > e->cap)
-    return hs::fail(HS_ERR_INVALID, "extract yields " + std::to_string(n) + " keys, capacity is " + std::to_string(e->cap));
-  e->cur ^= 1;
-  e->n = n;
+  HS_TRY(launch_desc(e, r));
+  return finish_extract(e, n_keys, false);
+}
+
+// ---- the UseFAST branch
+
+int check_fast_params(const hs_fast_params* p) {
+  if (!p) return hs::fail(HS_ERR_INVALID, "null params");
+  if (p->threshold < 0 || p->threshold > 254) return hs::fail(HS_ERR_INVALID, "threshold must lie in [0, 254]");
+  if (p->num_features < 2) return hs::fail(HS_ERR_INVALID, "num_features must be >= 2");
+  if (p->min_dist < 0) return hs::fail(HS_ERR_INVALID, "min_dist must be >= 0");
+  if (!(p->tolerance >= 0.f && p->tolerance < 1.f)) return hs::fail(HS_ERR_INVALID, "tolerance must lie in [0, 1)");
   return HS_OK;
+}
+
+// the detector's buffers, on the first fast extract: an extractor that never detects pays nothing
+// A retry after a failure half-way allocates again from the start; hs::Pool::alloc on a slot it already holds
+// releases that allocation first, so nothing is held twice.
+int ensure_fast(hs_extractor* e) {
+  if (e->have_fast) return HS_OK;
+  hs::Pool& m = e->pool;
+  const int W = e->W, H = e->H;
+  const size_t area = (size_t)W * H;
+  e->max_corners = ((W - 2 * kFastRing + 1) / 2) * ((H - 2 * kFastRing + 1) / 2);
+  const size_t mc = e->max_corners;
+  // Ssc's widths.  The bracket's `high` falls as K grows, so its value at K = 2 bounds every search: one workgroup,
+  // one covered grid and one taken list per width up to it.  Corners taken at one width have cells that differ by
+  // 3 or more in a row or a column, so a grid of R x C cells takes at most ceil(R/3) * ceil(C/3) of them.
+  const double exp1 = H + W + 4.0;
+  const double exp2 = 4.0 * W + 8.0 + 8.0 * H + (double)H * H + (double)W * W - 2.0 * H * W + 8.0 * H * W;
+  e->max_high = std::max(1, (int)-std::round(exp1 - std::sqrt(exp2)));
+  std::vector<size_t> woff(e->max_high), toff(e->max_high);
+  size_t cov = 0, tak = 0;
+  for (int w = 1; w <= e->max_high; w++) {
+    const size_t R = 2 * H / w + 1, C = 2 * W / w + 1;
+    woff[w - 1] = cov;
+    toff[w - 1] = tak;
+    cov += (R * C + 15) / 16 * 16;
+    tak += std::min(mc, ((R + 2) / 3) * ((C + 2) / 3));
+  }
+  HS_TRY(m.alloc(&e->d_resp, area));
+  HS_TRY(m.alloc(&e->d_occ, area));
+  HS_TRY(m.alloc(&e->d_covered, cov));
+  HS_TRY(m.alloc(&e->d_wtaken, tak));
+  HS_TRY(m.alloc(&e->d_wcnt, e->max_high));
+  HS_TRY(m.alloc(&e->d_woff, e->max_high));
+  HS_TRY(m.alloc(&e->d_toff, e->max_high));
+  HS_TRY(m.alloc(&e->d_frow_cnt, H - 2 * kFastRing));
+  HS_TRY(m.alloc(&e->d_cidx, mc));
+  HS_TRY(m.alloc(&e->d_cresp, mc));
+  for (hs_extract_result& r : e->res) {
+    HS_TRY(m.alloc(&r.response, e->alloc));
+    HS_TRY(m.alloc(&r.s_idx, mc));
+    HS_TRY(m.alloc(&r.s_resp, mc));
+    HS_TRY(m.alloc(&r.info, kFastInfoSize));
+  }
+  const size_t tb = sizeof(size_t) * e->max_high;
+  HS_HIP(hipMemcpyAsync(e->d_woff, woff.data(), tb, hipMemcpyHostToDevice, e->stream));
+  HS_HIP(hipMemcpyAsync(e->d_toff, toff.data(), tb, hipMemcpyHostToDevice, e->stream));
+  HS_HIP(hipStreamSynchronize(e->stream));  // the tables are locals
+  e->h_toff = toff;
+  e->have_fast = true;
+  return HS_OK;
+}
+
+// as run_extract, the keys coming from the detector; cvImgL is on the device or enqueued on e->stream (u: made here)
+int run_fast(hs_extractor* e, const hs_fast_params* p, hs_undistorter* u, const uint8_t* raw, int* n_keys) {
+  hs_extract_result& r = e->res[e->cur ^ 1];
+  hipStream_t s = e->stream;
+  HS_HIP(hipEventRecord(e->e0, s));
+  if (u) HS_HIP(hs_undist_enqueue(u, s, raw, nullptr, e->d_img));
+  HsFastArgs a;
+  a.W = e->W;
+  a.H = e->H;
+  a.threshold = p->threshold;
+  a.num_features = p->num_features;
+  a.min_dist = std::min(p->min_dist, std::max(e->W, e->H));  // beyond the image's larger side nothing changes
+  a.cap = e->alloc;
+  a.tolerance = p->tolerance;
+  a.img = e->d_img;
+  a.resp = e->d_resp;
+  a.row_cnt = e->d_frow_cnt;
+  a.c_idx = e->d_cidx;
+  a.c_resp = e->d_cresp;
+  a.s_idx = r.s_idx;
+  a.s_resp = r.s_resp;
+  a.max_high = e->max_high;
+  a.woff = e->d_woff;
+  a.toff = e->d_toff;
+  a.covered = e->d_covered;
+  a.wtaken = e->d_wtaken;
+  a.wcnt = e->d_wcnt;
+  a.occ = e->d_occ;
+  a.info = r.info;
+  a.x = r.x;
+  a.y = r.y;
+  a.response = r.response;
+  a.count = e->d_count;
+  const int rows = e->H - 2 * kFastRing;
+  HS_HIP(hipMemsetAsync(e->d_occ, 0, (size_t)e->W * e->H, s));
+  hipLaunchKernelGGL(hs_k_fast_resp, dim3((e->W + kFastTileW - 1) / kFastTileW, (e->H + kFastTileH - 1) / kFastTileH),
+                     dim3(256), 0, s, a);
+  HS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(hs_k_fast_count, dim3((rows + 3) / 4), dim3(256), 0, s, a);
+  HS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(hs_k_fast_write, dim3((rows + 3) / 4), dim3(256), 0, s, a);
+  HS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(hs_k_fast_sort, dim3(1), dim3(256), 0, s, a);
+  HS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(hs_k_fast_ssc, dim3(e->max_high), dim3(64), 0, s, a);
+  HS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(hs_k_fast_final, dim3(1), dim3(64), 0, s, a);
+  HS_HIP(hipGetLastError());
+  HS_TRY(launch_blur(e, r));
+  HS_TRY(launch_desc(e, r));
+  return finish_extract(e, n_keys, true);
 }
 
 // A consumer (hs_tracer_add_keys) may still be reading the current result set on its own stream.  This extract
@@ -288,6 +442,98 @@ int hs_extractor_extract_image(hs_extractor* e, hs_selector* s, hs_image* im, in
   HS_HIP(hipMemcpyAsync(e->d_img, v.img8, (size_t)e->W * e->H, hipMemcpyDeviceToDevice, e->stream));
   HS_HIP(hs_image_consumed(im, e->stream));
   return run_extract(e, d_map, nullptr, nullptr, n_keys);
+}
+
+void hs_fast_params_default(hs_fast_params* p) {
+  if (!p) return;
+  p->threshold = 8;       // minThFAST
+  p->num_features = 3000; // IndNumFeatures
+  p->min_dist = 5;        // EnforcedMinDist
+  p->tolerance = 0.1f;
+}
+
+int hs_extractor_extract_fast(hs_extractor* e, const hs_fast_params* p, const uint8_t* img8, int* n_keys) {
+  if (!e || !img8) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(check_fast_params(p));
+  HS_TRY(begin_extract(e));
+  HS_TRY(ensure_fast(e));
+  HS_HIP(hipMemcpyAsync(e->d_img, img8, (size_t)e->W * e->H, hipMemcpyHostToDevice, e->stream));
+  return run_fast(e, p, nullptr, nullptr, n_keys);
+}
+
+int hs_extractor_extract_fast_u8(hs_extractor* e, const hs_fast_params* p, hs_undistorter* u, const uint8_t* raw,
+                                 int* n_keys) {
+  if (!e || !u || !raw) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(check_fast_params(p));
+  HS_TRY(hs_undist_match(u, e->device, e->W, e->H));
+  HS_TRY(begin_extract(e));
+  HS_TRY(ensure_fast(e));
+  return run_fast(e, p, u, raw, n_keys);
+}
+
+int hs_extractor_extract_fast_image(hs_extractor* e, const hs_fast_params* p, hs_image* im, int* n_keys) {
+  if (!e || !im) return hs::fail(HS_ERR_INVALID, "null argument");
+  HS_TRY(check_fast_params(p));
+  HsImageView v;
+  HS_TRY(hs_image_view(im, e->device, e->W, e->H, 1, true, &v));
+  HS_TRY(begin_extract(e));
+  HS_TRY(ensure_fast(e));
+  HS_HIP(hipStreamWaitEvent(e->stream, v.ready, 0));
+  HS_HIP(hipMemcpyAsync(e->d_img, v.img8, (size_t)e->W * e->H, hipMemcpyDeviceToDevice, e->stream));
+  HS_HIP(hs_image_consumed(im, e->stream));
+  return run_fast(e, p, nullptr, nullptr, n_keys);
+}
+
+int hs_extractor_get_fast(hs_extractor* e, int* n_corners, int* width, float* response, float* corner_xy,
+                          float* corner_response) {
+  if (!e) return hs::fail(HS_ERR_INVALID, "null extractor");
+  const hs_extract_result& r = e->res[e->cur];
+  if (!r.fast) return hs::fail(HS_ERR_STATE, "the current result is not a fast extract");
+  HS_HIP(hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  int info[kFastInfoSize] = {0};
+  HS_HIP(hipMemcpyAsync(info, r.info, sizeof(info), hipMemcpyDeviceToHost, s));
+  if (response && e->n) HS_HIP(hipMemcpyAsync(response, r.response, (size_t)e->n * sizeof(float), hipMemcpyDeviceToHost, s));
+  HS_HIP(hipStreamSynchronize(s));
+  const size_t nc = info[kFastInfoCorners];
+  if (n_corners) *n_corners = (int)nc;
+  if (width) *width = info[kFastInfoWidth];
+  if ((corner_xy || corner_response) && nc) {
+    std::vector<int> idx(nc);
+    std::vector<uint8_t> resp(nc);
+    HS_HIP(hipMemcpyAsync(idx.data(), r.s_idx, nc * sizeof(int), hipMemcpyDeviceToHost, s));
+    HS_HIP(hipMemcpyAsync(resp.data(), r.s_resp, nc, hipMemcpyDeviceToHost, s));
+    HS_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < nc; i++) {
+      if (corner_xy) {
+        corner_xy[2 * i] = (float)(idx[i] % e->W);
+        corner_xy[2 * i + 1] = (float)(idx[i] / e->W);
+      }
+      if (corner_response) corner_response[i] = (float)resp[i];
+    }
+  }
+  return HS_OK;
+}
+
+// Test hook (not in the header): Ssc's bracket of the current fast result and what hs_k_fast_ssc left for width w,
+// valid until the next fast extract call.  *count = -1 for a width outside [low, high]: no workgroup evaluated it.
+// taken (nullable): the first min(*count, taken_cap) sorted indices that width took.
+int hs_debug_fast_width(hs_extractor* e, int w, int* low, int* high, int* count, int* taken, int taken_cap) {
+  if (!e || !low || !high || !count) return hs::fail(HS_ERR_INVALID, "null argument");
+  const hs_extract_result& r = e->res[e->cur];
+  if (!r.fast) return hs::fail(HS_ERR_STATE, "the current result is not a fast extract");
+  HS_HIP(hipSetDevice(e->device));
+  int info[kFastInfoSize] = {0};
+  HS_HIP(hipMemcpy(info, r.info, sizeof(info), hipMemcpyDeviceToHost));
+  *low = info[kFastInfoLow];
+  *high = info[kFastInfoHigh];
+  *count = -1;
+  if (w < *low || w > *high || w < 1 || w > e->max_high) return HS_OK;
+  HS_HIP(hipMemcpy(count, e->d_wcnt + (w - 1), sizeof(int), hipMemcpyDeviceToHost));
+  const int m = std::min(*count, taken_cap);
+  if (taken && m > 0)
+    HS_HIP(hipMemcpy(taken, e->d_wtaken + e->h_toff[w - 1], sizeof(int) * m, hipMemcpyDeviceToHost));
+  return HS_OK;
 }
 
 int hs_extractor_get(hs_extractor* e, int* n, float* xy, float* angle, uint8_t* desc, uint8_t* blurred) {

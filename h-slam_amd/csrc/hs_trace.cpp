@@ -261,7 +261,8 @@ int hs_tracer_add_keys(hs_tracer* t, hs_extractor* e, int slot, int* n_added) {
   if (n == 0) return HS_OK;
   HS_HIP(hipSetDevice(t->device));
   const int f = t->n;
-  // keys lie >= 19 px from every edge (include/hs_extract.h): add_points' border rule holds by construction
+  // keys lie >= 19 px from the left and top edges and >= 18 px from the right and bottom ones (a fast extract keeps
+  // x = W-19 / y = H-19, include/hs_extract.h): add_points' border rule, which needs 3 px, holds by construction
   HS_HIP(hipStreamWaitEvent(t->stream, ready, 0));
   HS_HIP(hipMemcpyAsync(t->d_u + f, d_x, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));
   HS_HIP(hipMemcpyAsync(t->d_v + f, d_y, sizeof(float) * n, hipMemcpyDeviceToDevice, t->stream));

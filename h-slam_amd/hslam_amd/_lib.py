@@ -62,6 +62,10 @@ class hs_undist_calib(C.Structure):  # include/hs_undist.h
                 ("desired_K", C.c_double * 4)]
 
 
+class hs_fast_params(C.Structure):  # include/hs_extract.h
+    _fields_ = [("threshold", C.c_int), ("num_features", C.c_int), ("min_dist", C.c_int), ("tolerance", C.c_float)]
+
+
 class hs_map_record(C.Structure):  # include/hs_map.h
     _fields_ = [("handle", C.c_int32), ("frame_id", C.c_int32), ("status", C.c_int32), ("numGoodResiduals", C.c_int32),
                 ("u", C.c_float), ("v", C.c_float), ("idepth", C.c_float), ("idepth_zero", C.c_float),
@@ -226,6 +230,13 @@ SIGNATURES = {
     "hs_extractor_extract_u8": ([VP, VP, VP, VP, VP], I),
     "hs_extractor_get": ([VP] * 6, I),
     "hs_extractor_last_stats": ([VP, VP], I),
+    "hs_fast_params_default": ([VP], None),
+    "hs_extractor_extract_fast": ([VP, VP, VP, VP], I),
+    "hs_extractor_extract_fast_u8": ([VP, VP, VP, VP, VP], I),
+    "hs_extractor_extract_fast_image": ([VP, VP, VP, VP], I),
+    "hs_extractor_get_fast": ([VP] * 6, I),
+    # test hook (not in the header): one width of the last fast extract's Ssc search
+    "hs_debug_fast_width": ([VP, I, VP, VP, VP, VP, I], I),
     "hs_tracer_add_keys": ([VP, VP, I, VP], I),
     # include/hs_flow.h
     "hs_flow_create": ([VP, I, I, I, I], I),
